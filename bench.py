@@ -194,6 +194,49 @@ def train_step(model, opt, batch, lr_policy, it, world):
     return step_body(model, opt, batch, world)
 
 
+DUMP_SAMPLE = 1 << 21       # entries of the parameter / gradient sample (8 MB each in float32)
+
+
+def dump_sample_index(total):
+    """Positions in the flattened parameters that --dump-outputs writes: all of them, or a fixed seeded sample."""
+    import numpy as np
+    if total <= DUMP_SAMPLE:
+        return np.arange(total, dtype=np.int64)
+    return np.unique(np.random.default_rng(20240).integers(0, total, size=DUMP_SAMPLE, dtype=np.int64))
+
+
+def dump_outputs(out_dir, model, loss):
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy, so that two builds can be compared
+    output for output (same arguments = same seeded model and batch).
+        loss.npy        float64 [1]   the step's loss
+        parameters.npy  float32 [n]   the updated parameters, flattened in named_parameters() order
+        gradients.npy   float32 [n]   the step's gradients at the same positions (0 where a parameter got none)
+        buffers.npy     float64 [m]   every floating-point buffer (BatchNorm running statistics), flattened
+    n = every parameter, or the fixed seeded sample of positions dump_sample_index() returns when there are more than
+    DUMP_SAMPLE (about 16 MB in all).  Returns the list of names written."""
+    import numpy as np
+    net = getattr(model, "module", model)
+    params = list(net.parameters())
+    if params[0].is_cuda:
+        torch.cuda.synchronize()
+    idx = dump_sample_index(sum(p.numel() for p in params))
+    sel = torch.from_numpy(idx).to(params[0].device)
+    flat_p = torch.cat([p.detach().float().reshape(-1) for p in params])
+    flat_g = torch.cat([(p.grad.detach().float() if p.grad is not None else torch.zeros_like(p, dtype=torch.float32))
+                        .reshape(-1) for p in params])
+    bufs = [b.detach().double().reshape(-1) for b in net.buffers() if b.is_floating_point()]
+    arrays = {
+        "loss": np.array([float(loss.detach().float().item())], dtype=np.float64),
+        "parameters": flat_p[sel].cpu().numpy().astype(np.float32),
+        "gradients": flat_g[sel].cpu().numpy().astype(np.float32),
+        "buffers": (torch.cat(bufs).cpu().numpy() if bufs else np.zeros(0)).astype(np.float64),
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
 class GraphedStep(object):
     """zero_grad -> forward -> backward (incl. collectives) captured once into a hipGraph and replayed, which removes
     ~650 host-side launches per step.  With opt_inside (FusedSGD: its learning rates live in a device vector,
@@ -863,6 +906,9 @@ def main():
                          "tsg_comm on a 1-rank RCCL group) -> config.forced_collectives; 0 = skip")
     ap.add_argument("--optimizer", default="fused", choices=["fused", "torch"])
     ap.add_argument("--trace-loss", action="store_true", help="debug: print the loss of every timed step (syncs)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (loss, parameters, gradients, "
+                         "BatchNorm buffers) as DIR/<name>.npy (rank 0; see dump_outputs)")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--miopen-find", type=int, default=int(os.environ.get("TSG_MIOPEN_FIND", "-1")),
                     help="torch.backends.cudnn.benchmark (train.py:35); 0 = immediate mode on the shipped MIOpen find-db (same "
@@ -1074,6 +1120,9 @@ def main():
         sync()
         dt = time.perf_counter() - t0
         final_loss = float(loss.item())
+        dumped = None
+        if args.dump_outputs and rank == 0:                            # before the side runs below step the model again
+            dumped = dump_outputs(args.dump_outputs, model, loss)
         eager_rec = None
         if graphed is not None:
             # Replayed launches cannot be bracketed from the host.  The same step, eager, right behind the replayed region on
@@ -1223,6 +1272,8 @@ def main():
                        "hip_graph_fallback": graph_fallback, "eager_steps": eager_rec,
                        "forced_collectives": None, "optimizer": args.optimizer},
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if timer is not None:
             # the dominant kernel FAMILY (all bn_* passes are one family: SyncBN) from the fully instrumented last warm-up
             # step, the three largest families beside it; `timed_region` = the family's largest label bracketed with HIP

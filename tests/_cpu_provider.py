@@ -67,6 +67,11 @@ class OracleProvider:
         mean, invstd = mean.float(), invstd.float()
         return mean, invstd, self._pack(mean, invstd, gamma, beta)
 
+    def bn_mixed_supported(self, x):
+        """No mixed-layout (NCHW in, channels_last out) pass here: syncbn.PREFER_CHANNELS_LAST_OUTPUT stays True after a
+        GPU test's DistributedDataParallel set it, and the plain NCHW pass must then be taken."""
+        return False
+
     def bn_affine(self, mean, invstd, gamma, beta):
         return self._pack(mean, invstd, gamma, beta)
 

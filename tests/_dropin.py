@@ -8,9 +8,11 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import stage_reference as _sr  # noqa: E402
+
+REF = _sr.REF                   # the reference checkout (TSG_REFERENCE_DIR overrides, as in tools/stage_reference.py)
+GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 
 def have_reference():
@@ -37,9 +39,23 @@ def stage(tmp_path, family, exp, files=("config.py", "network.py")):
     return _sr.stage(tmp_path, family, exp, files)
 
 
-def run_in(exp_dir, script, timeout=600):
+def golden():
+    """What the reference's own files computed in the scripts of tests/test_dropin_cpu.py (tests/golden/
+    make_dropin_golden.py): the checks those tests make where the reference checkout is absent."""
+    import json
+    import numpy as np
+    with open(os.path.join(GOLDEN, "dropin_golden.json")) as fh:
+        g = json.load(fh)
+    g["arrays"] = dict(np.load(os.path.join(GOLDEN, "dropin_golden.npz")))
+    return g
+
+
+def run_in(exp_dir, script, timeout=600, furnace=False):
+    """`furnace`: our furnace/ on the path from the start (what the reference's config.py does when it is staged)."""
     env = dict(os.environ)
     paths = [ROOT, os.path.join(ROOT, "torchseg_amd", "shims")]
+    if furnace:
+        paths.append(os.path.join(ROOT, "torchseg_amd", "furnace"))
     import importlib.util
     if importlib.util.find_spec("cv2") is None:                 # the stand-in must never shadow a real OpenCV
         paths.append(os.path.join(ROOT, "torchseg_amd", "shims_optional"))

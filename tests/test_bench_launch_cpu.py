@@ -47,3 +47,38 @@ def test_world_size_mismatch_is_refused():
 def test_defaults_follow_survey_8d():
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert '"--steps", type=int, default=50' in src and '"--warmup", type=int, default=20' in src
+
+
+def test_dump_outputs_writes_the_step_results(tmp_path):
+    """--dump-outputs: loss, a fixed sample of the parameters and their gradients at the same positions, the floating-point
+    buffers; float32 / float64 only, the same sample positions on every call, under 64 MB."""
+    import numpy as np
+    import torch
+    import torch.nn as nn
+    sys.path.insert(0, ROOT)
+    import bench
+    torch.manual_seed(0)
+    net = nn.Sequential(nn.Conv2d(3, 8, 3), nn.BatchNorm2d(8), nn.Conv2d(8, 4, 1), nn.Conv2d(4, 4, 1))
+    loss = net[:3](torch.randn(2, 3, 8, 8)).square().mean()
+    loss.backward()                                  # net[3] gets no gradient: dumped as zeros
+    names = bench.dump_outputs(str(tmp_path / "a"), net, loss)
+    assert names == ["buffers", "gradients", "loss", "parameters"]
+    a = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in names}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    flat = torch.cat([p.detach().reshape(-1) for p in net.parameters()]).numpy()
+    assert a["loss"].dtype == np.float64 and a["loss"][0] == float(loss)
+    assert a["parameters"].dtype == np.float32 and np.array_equal(a["parameters"], flat)
+    assert a["gradients"].dtype == np.float32 and a["gradients"].shape == a["parameters"].shape
+    assert np.array_equal(a["gradients"][-(16 + 4):], np.zeros(20, np.float32))
+    assert a["buffers"].dtype == np.float64 and a["buffers"].size == 16
+    big = nn.Linear(1500, 1500)                      # 2.25 M entries > DUMP_SAMPLE: a seeded sample
+    loss = big(torch.randn(2, 1500)).sum()
+    loss.backward()
+    bench.dump_outputs(str(tmp_path / "b"), big, loss)
+    bench.dump_outputs(str(tmp_path / "c"), big, loss)
+    idx = bench.dump_sample_index(1500 * 1501)
+    assert np.array_equal(idx, bench.dump_sample_index(1500 * 1501)) and 0 < idx.size <= bench.DUMP_SAMPLE
+    flat = torch.cat([p.detach().reshape(-1) for p in big.parameters()]).numpy()
+    for d in ("b", "c"):
+        assert np.array_equal(np.load(str(tmp_path / d / "parameters.npy")), flat[idx])
+    assert sum(os.path.getsize(str(tmp_path / "b" / f)) for f in os.listdir(str(tmp_path / "b"))) < 64 << 20

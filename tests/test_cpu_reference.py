@@ -1,20 +1,18 @@
 """bench.py's cpu_baseline of kind "reference": tools/cpu_reference.py runs the REFERENCE'S OWN network.py / seg_oprs.py /
 resnet.py / loss_opr.py (staged by tools/stage_reference.py) on the host.  Checked here: it runs from the checkout AND from
 the archive the GPU box gets, imports the reference's modules (not ours), and its first loss equals the oracle port's
-(same seed, same synthetic batch) — the two CPU legs time the same arithmetic."""
+(same seed, same synthetic batch) — the two CPU legs time the same arithmetic.  Where neither is present, the port is held
+to the parameter count and first loss that leg recorded (tests/golden/dropin_golden.json, make_dropin_golden.py)."""
 import json
 import os
 import subprocess
 import sys
 
-import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import stage_reference  # noqa: E402
-
-pytestmark = pytest.mark.skipif(not stage_reference.available(), reason="neither /root/reference nor the staged archive")
 
 
 def _run(env_extra):
@@ -36,9 +34,12 @@ def test_reference_leg_from_archive_and_checkout_equals_the_port():
     if stage_reference.have_reference():
         recs.append(_run({}))
         assert recs[-1]["source"] == "reference checkout"
-    assert recs
     for r in recs:
         assert r["kind"] == "reference" and r["params"] == 13494777 and r["value"] > 0     # 13.49 M parameters
+    if not recs:                                                           # neither: what that leg computed, stored
+        with open(os.path.join(ROOT, "tests", "golden", "dropin_golden.json")) as fh:
+            recs.append(json.load(fh)["cpu_reference"])
+        assert recs[-1]["params"] == 13494777
     import torch.nn as nn
     sys.path.insert(0, ROOT)
     import bench
@@ -50,5 +51,6 @@ def test_reference_leg_from_archive_and_checkout_equals_the_port():
     model.train()
     imgs, gts = bench.synthetic_batch(torch.device("cpu"), 2, 128)
     loss = float(model(imgs, gts).item())
+    assert sum(p.numel() for p in model.parameters()) == 13494777
     for r in recs:
         assert abs(r["first_loss"] - loss) <= 1e-5 * abs(loss), (r["first_loss"], loss)
