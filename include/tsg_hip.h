@@ -808,6 +808,26 @@ int tsg_edge_labels(const void* gt, const int32_t* geom, const double* inv_scale
                     int threshold1, int threshold2, int aperture, int dilate_size, int pad_label, void* out, int out_type,
                     void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Depthwise 3x3 convolution (csrc/dwconv.hip) — replaces the library calls behind the
+ * `nn.Conv2d(C, C, 3, stride, 1, groups=C, bias=False)` layers of furnace/base_model/xception.py:10-26
+ * (SeparableConvBnRelu.conv1, 51 of them in xception39), forward and backward.  Activations channels_last
+ * [B, H, W, C] with C % 8 == 0, 16-byte aligned; H, W: input size, output ((H - 1) / stride + 1, (W - 1) / stride + 1);
+ * w: the fp32 parameter [C, 1, 3, 3] (element c*9 + kh*3 + kw); dw: fp32, same element order.  dtype TSG_BF16: bf16
+ * activations, fp32 accumulation, one rounding; TSG_F32 (parity mode): fp32 activations, exact products, fp64
+ * accumulation, one rounding.  The weight gradient writes per-block partials [P][9][C] (fp32 / fp64) to `ws` and folds
+ * them in slice order in a second launch; P is a function of the shape only.  No atomics: every result is
+ * bit-reproducible. */
+int    tsg_dwconv3x3_supported(int dtype, int C, int kh, int kw, int stride, int pad, int dilation, int groups, int H,
+                               int W);
+int    tsg_dwconv3x3_fwd(const void* x, const float* w, void* y, int dtype, int64_t B, int H, int W, int C, int stride,
+                         void* stream);
+int    tsg_dwconv3x3_dgrad(const void* dy, const float* w, void* dx, int dtype, int64_t B, int H, int W, int C, int stride,
+                           void* stream);
+size_t tsg_dwconv3x3_wgrad_ws_bytes(int64_t B, int H, int W, int C, int stride, int dtype);
+int    tsg_dwconv3x3_wgrad(const void* x, const void* dy, float* dw, int dtype, int64_t B, int H, int W, int C, int stride,
+                           void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

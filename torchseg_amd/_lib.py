@@ -182,6 +182,11 @@ _PROTOS = {
     "tsg_conv2d_f32_exact_dgrad": (_i, [_p, _p, _p, _i64] + [_i] * 12 + [_p, _p, _p, _p]),
     "tsg_conv2d_f32_exact_wgrad_ws_bytes": (_sz, [_i64] + [_i] * 12),
     "tsg_conv2d_f32_exact_wgrad": (_i, [_p, _p, _p, _i64] + [_i] * 12 + [_p, _p, _p, _p, _sz, _p]),
+    "tsg_dwconv3x3_supported": (_i, [_i] * 10),
+    "tsg_dwconv3x3_fwd": (_i, [_p, _p, _p, _i, _i64, _i, _i, _i, _i, _p]),
+    "tsg_dwconv3x3_dgrad": (_i, [_p, _p, _p, _i, _i64, _i, _i, _i, _i, _p]),
+    "tsg_dwconv3x3_wgrad_ws_bytes": (_sz, [_i64, _i, _i, _i, _i, _i]),
+    "tsg_dwconv3x3_wgrad": (_i, [_p, _p, _p, _i, _i64, _i, _i, _i, _i, _p, _sz, _p]),
 }
 
 _lib = None

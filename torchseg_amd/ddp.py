@@ -54,6 +54,8 @@ upsample overrides.  Controlled by env so train.py needs no edit:
                         the first one's BatchNorm + ReLU while its own convolution loads its input; fusion.PendingCbr)
   TSG_SPLIT_BIAS=1|0    (default 1 on GPU: conv bias add / bias grad through our column-sum kernel)
   TSG_STEM_CONV=1|0     (default 1 on GPU: 7x7/2 image stems on tsg_stem_conv_* instead of MIOpen)
+  TSG_DW_CONV=1|0       (default 1 on GPU: depthwise 3x3 convolutions (Xception39) on tsg_dwconv3x3_*: reproducible weight
+                        gradient, exact fp32 parity mode; dwconv.py)
   TSG_ADAPTIVE_POOL=1|0 (default 1 on GPU: nn.AdaptiveAvgPool2d on channels_last maps -> tsg_adaptive_avgpool_nhwc_*)
   TSG_CONV_WRW=1|0      (default 1 on GPU: weight gradient of the 64->64 3x3/1 convolutions on tsg_conv3x3_wrw;
                         TSG_CONV_WRW_IMPL=gen|tr|v1 picks the kernel of the 64 -> 64 layers, default gen)
@@ -412,6 +414,9 @@ class DistributedDataParallel(nn.Module):
             if _env_flag("TSG_STEM_CONV", True):
                 from .stemconv import install_stem_conv
                 install_stem_conv(self.module)
+            if _env_flag("TSG_DW_CONV", True):
+                from .dwconv import install_depthwise_conv
+                install_depthwise_conv(self.module)                  # depthwise 3x3 layers (Xception39): ours, reproducible
             if _env_flag("TSG_CONV_WRW", True):
                 from .convwrw import install_conv_wrw
                 install_conv_wrw(self.module)

@@ -44,6 +44,11 @@ def _require_contiguous(*tensors):
                              % (tuple(t.stride()), tuple(t.shape)))
 
 
+def _dw_filter_dense(w):
+    """[C,1,3,3] whose element (c, 0, kh, kw) sits at c*9 + kh*3 + kw (contiguous and channels_last alike)"""
+    return w.stride(0) == 9 and w.stride(2) == 3 and w.stride(3) == 1
+
+
 def _label_code(t):
     if t.dtype == torch.int64:
         return L.I64
@@ -870,6 +875,46 @@ class HipKernels:
         L.check(self.lib.tsg_conv2d_f32_exact_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, *geo,
                                                     self._strides4(x), self._strides4(dw), self._strides4(dy),
                                                     ws.data_ptr(), wsb, L.stream_ptr(x)), "tsg_conv2d_f32_exact_wgrad")
+        return dw
+
+    # ---- depthwise 3x3 convolution (Xception39; csrc/dwconv.hip) ---------------
+    def dwconv3x3_supported(self, x, weight, stride, padding, dilation, groups):
+        """x [B,C,H,W] channels_last bf16 / fp32, weight fp32 [C,1,3,3]; hyper-parameters as square ints"""
+        if (x.dim() != 4 or weight.dim() != 4 or x.dtype not in (torch.bfloat16, torch.float32)
+                or weight.dtype != torch.float32 or not x.is_contiguous(memory_format=torch.channels_last)
+                or tuple(weight.shape) != (x.shape[1], 1, 3, 3) or not _dw_filter_dense(weight)):
+            return False
+        return bool(self.lib.tsg_dwconv3x3_supported(L.dtype_code(x), x.shape[1], weight.shape[2], weight.shape[3], stride,
+                                                     padding, dilation, groups, x.shape[2], x.shape[3]))
+
+    def dwconv3x3_fwd(self, x, weight, stride):
+        """x [B,C,H,W] channels_last, weight fp32 [C,1,3,3] -> y [B,C,OH,OW] channels_last, x's dtype"""
+        B, Cc, H, W = x.shape
+        y = torch.empty((B, Cc, (H - 1) // stride + 1, (W - 1) // stride + 1), dtype=x.dtype, device=x.device,
+                        memory_format=torch.channels_last)
+        L.check(self.lib.tsg_dwconv3x3_fwd(x.data_ptr(), weight.data_ptr(), y.data_ptr(), L.dtype_code(x), B, H, W, Cc,
+                                           stride, L.stream_ptr(x)), "tsg_dwconv3x3_fwd")
+        return y
+
+    def dwconv3x3_dgrad(self, dy, weight, x_like, stride):
+        """dy [B,C,OH,OW] channels_last (x's dtype) -> dx shaped like x_like, channels_last"""
+        B, Cc, H, W = x_like.shape
+        dx = torch.empty((B, Cc, H, W), dtype=dy.dtype, device=dy.device, memory_format=torch.channels_last)
+        L.check(self.lib.tsg_dwconv3x3_dgrad(dy.data_ptr(), weight.data_ptr(), dx.data_ptr(), L.dtype_code(dy), B, H, W,
+                                             Cc, stride, L.stream_ptr(dy)), "tsg_dwconv3x3_dgrad")
+        return dx
+
+    def dwconv3x3_wgrad(self, x, dy, weight, stride):
+        """-> dw fp32 with the parameter's shape and strides; the partials live in a workspace of the caching allocator"""
+        B, Cc, H, W = x.shape
+        dt = L.dtype_code(x)
+        wsb = self.lib.tsg_dwconv3x3_wgrad_ws_bytes(B, H, W, Cc, stride, dt)
+        if wsb == 0:
+            L.check(-3, "tsg_dwconv3x3_wgrad_ws_bytes")
+        ws = torch.empty(wsb, dtype=torch.uint8, device=x.device)
+        dw = torch.empty_like(weight)
+        L.check(self.lib.tsg_dwconv3x3_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), dt, B, H, W, Cc, stride,
+                                             ws.data_ptr(), wsb, L.stream_ptr(x)), "tsg_dwconv3x3_wgrad")
         return dw
 
     def sgd_step(self, param, grad, buf, lr, momentum, weight_decay, grad_scale, first):

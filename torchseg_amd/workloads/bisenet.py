@@ -81,9 +81,9 @@ class SpatialPath(nn.Module):
 class BiSeNetHead(nn.Module):
     """3x3 CBR -> 1x1 classifier -> bilinear x`scale` (network.py:140-168)."""
 
-    def __init__(self, in_planes, out_planes, scale, is_aux=False, norm_layer=nn.BatchNorm2d):
+    def __init__(self, in_planes, out_planes, scale, is_aux=False, norm_layer=nn.BatchNorm2d, aux_mid=256):
         super(BiSeNetHead, self).__init__()
-        mid = 256 if is_aux else 64
+        mid = aux_mid if is_aux else 64            # auxiliary heads: 256 in R18, 128 in X39 (X39 network.py:140-155)
         self.conv_3x3 = _cbr(in_planes, mid, 3, 1, 1, norm_layer)
         self.conv_1x1 = nn.Conv2d(mid, out_planes, kernel_size=1, stride=1, padding=0)
         self.scale = scale

@@ -1,0 +1,75 @@
+"""BiSeNet with the Xception39 context path (model/bisenet/cityscapes.bisenet.X39/network.py:18-168).
+
+Differs from the R18 builder (workloads/bisenet.py) in the backbone (furnace/base_model/xception.py: 1/8, 1/16 and 1/32
+stages of 64, 128 and 256 channels), the global-context and attention-refinement widths (256 -> 128, 128 -> 128), the
+auxiliary heads' 3x3 width (128) and the loss: all three heads use `ohem_criterion` (network.py:103-108).  SpatialPath,
+FeatureFusion and the heads are the R18 builder's.  Module attribute names and construction order match the reference file,
+hence state dicts are interchangeable and a fixed seed initialises both identically (tests/test_bisenet_x39_cpu.py).
+
+The `.speed` experiment (cityscapes.bisenet.X39.speed) is the same network with head scales 2 / 1 / 1 (labels at 1/8 of
+the crop): the unchanged network.py of that experiment builds on our furnace as it is.  Eager only: none of the R18
+builder's side-stream forks or segmented-graph hooks.
+"""
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import add_then_upsample, ensure_furnace_on_path
+from .bisenet import BiSeNetHead, SpatialPath, _cbr, _up
+
+ensure_furnace_on_path()
+from base_model import xception39  # noqa: E402
+from seg_opr.seg_oprs import AttentionRefinement, FeatureFusion  # noqa: E402
+
+
+class BiSeNetX39(nn.Module):
+    tsg_native_fusions = True      # calls the fused operators itself (workloads/__init__.py)
+
+    def __init__(self, out_planes, is_training, criterion, ohem_criterion, pretrained_model=None,
+                 norm_layer=nn.BatchNorm2d):
+        super(BiSeNetX39, self).__init__()
+        self.context_path = xception39(pretrained_model, norm_layer=norm_layer)
+        self.business_layer = []
+        self.is_training = is_training
+        self.spatial_path = SpatialPath(3, 128, norm_layer)
+        ch = 128
+        self.global_context = nn.Sequential(nn.AdaptiveAvgPool2d(1), _cbr(256, ch, 1, 1, 0, norm_layer))
+        arms = [AttentionRefinement(256, ch, norm_layer), AttentionRefinement(128, ch, norm_layer)]
+        refines = [_cbr(ch, ch, 3, 1, 1, norm_layer), _cbr(ch, ch, 3, 1, 1, norm_layer)]
+        heads = [BiSeNetHead(ch, out_planes, 16, True, norm_layer, aux_mid=128),
+                 BiSeNetHead(ch, out_planes, 8, True, norm_layer, aux_mid=128),
+                 BiSeNetHead(ch * 2, out_planes, 8, False, norm_layer)]
+        self.ffm = FeatureFusion(ch * 2, ch * 2, 1, norm_layer)
+        self.arms = nn.ModuleList(arms)
+        self.refines = nn.ModuleList(refines)
+        self.heads = nn.ModuleList(heads)
+        self.business_layer += [self.spatial_path, self.global_context, self.arms, self.refines,
+                                self.heads, self.ffm]
+        if is_training:
+            self.criterion = criterion
+            self.ohem_criterion = ohem_criterion
+
+    def features(self, data):
+        """-> [1/16 aux fm, 1/8 aux fm, fused 1/8 fm] (network.py:75-101)"""
+        spatial_out = self.spatial_path(data)
+        c8, c16, c32 = self.context_path(data)
+        f16 = self.refines[0](add_then_upsample(self.arms[0](c32), _up(self.global_context(c32), size=c32.shape[2:]),
+                                                c16.shape[2:]))
+        f8 = self.refines[1](add_then_upsample(self.arms[1](c16), f16, c8.shape[2:]))
+        return [f16, f8, self.ffm(spatial_out, f8)]
+
+    def forward(self, data, label=None):
+        f16, f8, fused = self.features(data)
+        if self.is_training:
+            aux0 = self.ohem_criterion(self.heads[0](f16), label)
+            aux1 = self.ohem_criterion(self.heads[1](f8), label)
+            main = self.ohem_criterion(self.heads[-1](fused), label)
+            return main + aux0 + aux1                      # network.py:108
+        return F.log_softmax(self.heads[-1](fused), dim=1)  # network.py:111
+
+    def logits(self, data):
+        """The three full-resolution head outputs (parity checks)."""
+        f16, f8, fused = self.features(data)
+        return self.heads[0](f16), self.heads[1](f8), self.heads[-1](fused)
+
+
+BiSeNet = BiSeNetX39
