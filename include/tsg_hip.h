@@ -828,6 +828,30 @@ size_t tsg_dwconv3x3_wgrad_ws_bytes(int64_t B, int H, int W, int C, int stride, 
 int    tsg_dwconv3x3_wgrad(const void* x, const void* dy, float* dw, int dtype, int64_t B, int H, int W, int C, int stride,
                            void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Segmentation head tail (csrc/segtail.hip) — replaces, for an evaluated window, the chain
+ * `F.log_softmax(F.interpolate(z, (H, W), mode='bilinear', align_corners=True), dim=1)` of the networks' eval forward,
+ * the flip pass, `torch.exp` and the window's `data[...] += score` of furnace/engine/evaluator.py:176-188 / :226-242.
+ * z, zflip: low-resolution logits [N, C, h, w] planar, TSG_F32 or TSG_BF16, 1 <= C <= 256.  The interpolated logit
+ * uses the taps and weights of tsg_upsample_bilinear_ac_fwd, formed in fp32 from the taps (no intermediate rounding).
+ *
+ * logprob: out [N, C, H, W] fp32 = log_softmax(interp(z), dim=1); out 16-byte aligned. */
+int tsg_seg_tail_logprob_supported(int dtype, int C, int h, int w, int H, int W);
+int tsg_seg_tail_logprob(const void* z, int dtype, int64_t N, int C, int h, int w, int H, int W, float* out,
+                         void* stream);
+/* accum: the evaluator's window step.  lp = log_softmax(interp(z)), lpf the same of zflip (NULL: the term is absent);
+ * geom: DEVICE int32 [N][6] = (oy, ox, t, l, rows, cols) per window n;
+ *   dst[c, oy+r, ox+q] (+)= exp(lp[n, c, t+r, l+q] + lpf[n, c, t+r, W-1-(l+q)]),  0 <= r < rows, 0 <= q < cols,
+ * dst fp32 [C, Hd, Wd].  Work is done per destination pixel of the region [by0, by1) x [bx0, bx1) (the union of the
+ * windows, which the caller knows): the covering windows are added in window order to one read of dst, the fp32
+ * summation order of a window-by-window `+=` loop; no atomics, bit-reproducible.  accumulate = 0: a pixel's first
+ * covering window writes instead of adding; pixels no window covers are not touched.  Window pixels outside
+ * [0, H) x [0, W) of the window, or outside the region, are skipped. */
+int tsg_seg_tail_accum_supported(int dtype, int C, int h, int w, int H, int W, int Hd, int Wd);
+int tsg_seg_tail_accum(const void* z, const void* zflip, int dtype, int64_t N, int C, int h, int w, int H, int W,
+                       const int32_t* geom, float* dst, int Hd, int Wd, int by0, int by1, int bx0, int bx1,
+                       int accumulate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -187,6 +187,10 @@ _PROTOS = {
     "tsg_dwconv3x3_dgrad": (_i, [_p, _p, _p, _i, _i64, _i, _i, _i, _i, _p]),
     "tsg_dwconv3x3_wgrad_ws_bytes": (_sz, [_i64, _i, _i, _i, _i, _i]),
     "tsg_dwconv3x3_wgrad": (_i, [_p, _p, _p, _i, _i64, _i, _i, _i, _i, _p, _sz, _p]),
+    "tsg_seg_tail_logprob_supported": (_i, [_i] * 6),
+    "tsg_seg_tail_logprob": (_i, [_p, _i, _i64, _i, _i, _i, _i, _i, _p, _p]),
+    "tsg_seg_tail_accum_supported": (_i, [_i] * 8),
+    "tsg_seg_tail_accum": (_i, [_p, _p, _i, _i64, _i, _i, _i, _i, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
 }
 
 _lib = None

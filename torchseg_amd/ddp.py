@@ -368,6 +368,41 @@ def _broadcast_coalesced(tensors, src, group):
                 off += t.numel()
 
 
+def install_kernels(module, compute_dtype):
+    """Re-class the network's layers onto our kernels (GPU only), in the order the DDP wrapper has always applied them:
+    split bias, stem, depthwise, 3x3 conv, adaptive pool, classifier, pooled 1x1, pointwise 1x1, and in fp32 (the parity
+    mode) the exact convolutions.  Shared by DistributedDataParallel and torchseg_amd.infer.prepare_inference."""
+    if _env_flag("TSG_SPLIT_BIAS", True):
+        from .convbias import split_conv_bias
+        split_conv_bias(module)
+    if _env_flag("TSG_STEM_CONV", True):
+        from .stemconv import install_stem_conv
+        install_stem_conv(module)
+    if _env_flag("TSG_DW_CONV", True):
+        from .dwconv import install_depthwise_conv
+        install_depthwise_conv(module)                  # depthwise 3x3 layers (Xception39): ours, reproducible
+    if _env_flag("TSG_CONV_WRW", True):
+        from .convwrw import install_conv_wrw
+        install_conv_wrw(module)
+    if _env_flag("TSG_ADAPTIVE_POOL", True):
+        from .pool import install_adaptive_pool
+        install_adaptive_pool(module)
+    if _env_flag("TSG_CLS_HEAD", True):
+        from .clshead import install_cls_head
+        install_cls_head(module)                        # 1x1 classifier convolutions -> planar logits
+    if _env_flag("TSG_VEC_CONV", True):
+        from .vecconv import install_pooled_conv
+        install_pooled_conv(module)                     # 1x1 convolutions of pooled [B, C, 1, 1] maps
+    if _env_flag("TSG_PW_CONV", True):
+        from .pwconv import install_pointwise_conv
+        install_pointwise_conv(module)                  # remaining full-map 1x1 layers: reproducible weight gradient
+    if compute_dtype == torch.float32:
+        # fp32 = the parity mode: convolutions on the reference-accuracy kernels (exactconv.py: logits 1.3-1.9e-5
+        # from the float64 truth, the reference's CPU path 7-8e-5, the vendor library's fp32 kernels 5-6e-5)
+        from . import exactconv
+        exactconv.install(module)
+
+
 class DistributedDataParallel(nn.Module):
     """See module docstring.  Positional/keyword arguments follow apex's wrapper;
     the ones that only tune apex's internal copies are accepted and ignored."""
@@ -408,35 +443,7 @@ class DistributedDataParallel(nn.Module):
             install_aten_overrides()
             from .psa import model_has_psa
             self.fuse_psa = _env_flag("TSG_FUSE_PSA", model_has_psa(module) and not native)
-            if _env_flag("TSG_SPLIT_BIAS", True):
-                from .convbias import split_conv_bias
-                split_conv_bias(self.module)
-            if _env_flag("TSG_STEM_CONV", True):
-                from .stemconv import install_stem_conv
-                install_stem_conv(self.module)
-            if _env_flag("TSG_DW_CONV", True):
-                from .dwconv import install_depthwise_conv
-                install_depthwise_conv(self.module)                  # depthwise 3x3 layers (Xception39): ours, reproducible
-            if _env_flag("TSG_CONV_WRW", True):
-                from .convwrw import install_conv_wrw
-                install_conv_wrw(self.module)
-            if _env_flag("TSG_ADAPTIVE_POOL", True):
-                from .pool import install_adaptive_pool
-                install_adaptive_pool(self.module)
-            if _env_flag("TSG_CLS_HEAD", True):
-                from .clshead import install_cls_head
-                install_cls_head(self.module)                        # 1x1 classifier convolutions -> planar logits
-            if _env_flag("TSG_VEC_CONV", True):
-                from .vecconv import install_pooled_conv
-                install_pooled_conv(self.module)                     # 1x1 convolutions of pooled [B, C, 1, 1] maps
-            if _env_flag("TSG_PW_CONV", True):
-                from .pwconv import install_pointwise_conv
-                install_pointwise_conv(self.module)                  # remaining full-map 1x1 layers: reproducible weight gradient
-            if self.compute_dtype == torch.float32:
-                # fp32 = the parity mode: convolutions on the reference-accuracy kernels (exactconv.py: logits 1.3-1.9e-5
-                # from the float64 truth, the reference's CPU path 7-8e-5, the vendor library's fp32 kernels 5-6e-5)
-                from . import exactconv
-                exactconv.install(self.module)
+            install_kernels(self.module, self.compute_dtype)
 
         self._fork_hooks = []
         if self.on_gpu and not native:

@@ -26,6 +26,29 @@ def _cv_round(v):
     return int(round(v))                          # cvRound: half to even
 
 
+def _tsg_infer():
+    """TSG_INFER=1 (default 0): run the network through torchseg_amd.infer.prepare_inference and, when its output is
+    the pending log_softmax of an up-sampled head, fuse the window tail (tsg_seg_tail_accum)."""
+    return os.environ.get("TSG_INFER", "0").strip() not in ("", "0")
+
+
+def _materialize(v):
+    from torchseg_amd.fusion import materialize
+    return materialize(v)
+
+
+def tail_geometry(chunk, margin, sh, sw, crop_size):
+    """Per window of a batch, (oy, ox, t, l, rows, cols) for tsg_seg_tail_accum into the [C, sh, sw] score map: the
+    window at (sy, sx) of the padded map, clipped to the image inside the margins -- what adding the window into the
+    padded map and slicing the margins off afterwards (scale_scores) selects."""
+    out = []
+    for sy, sx in chunk:
+        r0, r1 = max(sy, margin[0]), min(sy + crop_size, margin[0] + sh)
+        c0, c1 = max(sx, margin[2]), min(sx + crop_size, margin[2] + sw)
+        out.append((r0 - margin[0], c0 - margin[2], r0 - sy, c0 - sx, max(r1 - r0, 0), max(c1 - c0, 0)))
+    return np.array(out, dtype=np.int64).reshape(len(chunk), 6)
+
+
 class Evaluator(object):
     window_batch = 4                              # windows per network call (eval-mode BN: results do not depend on it)
 
@@ -110,8 +133,25 @@ class Evaluator(object):
             t = t.expand(t.shape[0], t.shape[1], 3)
         return t.to(self._device(device), dtype=torch.uint8).contiguous()
 
+    def _infer_func(self, device):
+        """TSG_INFER=1: the network prepared once per network and device (torchseg_amd.infer.prepare_inference)."""
+        from torchseg_amd.infer import prepare_inference
+        key = (id(self.val_func), str(device))
+        if getattr(self, "_infer_key", None) != key:
+            self.val_func.to(device)
+            self._infer_net = prepare_inference(self.val_func)
+            self._infer_key = key
+        return self._infer_net
+
     def _network_scores(self, x):
         """val_func_process (evaluator.py:255-273) on a batch [n,3,h,w]: log-probabilities, flip TTA, exp."""
+        if _tsg_infer():
+            net = self._infer_func(x.device)
+            with torch.no_grad():
+                score = torch.as_tensor(_materialize(net(x)))
+                if self.is_flip:
+                    score = score + _materialize(net(x.flip(-1))).flip(-1)
+                return torch.exp(score.float())
         # the reference moves the network to the input's device on every call (evaluator.py:258-259: an unchanged eval.py
         # builds it on the CPU and run() loads the checkpoint with map_location='cpu'); a no-op once it is there
         self.val_func.to(x.device)
@@ -121,6 +161,29 @@ class Evaluator(object):
             if self.is_flip:
                 score = score + self.val_func(x.flip(-1)).flip(-1)
             return torch.exp(score.float())
+
+    def _fused_window_scores(self, x, data, geom, crop_size, size):
+        """TSG_INFER=1: when the prepared network returns the pending log_softmax of an up-sampled head, the windows
+        (and their flipped pass) go into `data` ([C, *size], allocated on the first batch) through tsg_seg_tail_accum;
+        returns `data`, or None when the output is anything else."""
+        from torchseg_amd import kernels as K
+        from torchseg_amd.infer import pending_tail
+        net = self._infer_func(x.device)
+        with torch.no_grad():
+            tail = pending_tail(net(x))
+            if tail is None or tuple(tail[1]) != (crop_size, crop_size):
+                return None
+            z = tail[0].clone() if self.is_flip else tail[0]      # the flipped call may reuse the logits' memory
+            zf = None
+            if self.is_flip:
+                tf = pending_tail(net(x.flip(-1)))
+                if tf is None:
+                    return None
+                zf = tf[0]
+            if data is None:
+                data = torch.zeros((z.shape[1],) + tuple(size), dtype=torch.float32, device=x.device)
+            K.provider().seg_tail_accum(z, zf, geom, data, crop_size, crop_size, accumulate=True)
+        return data
 
     def val_func_process(self, input_data, device=None):
         """[3,h,w] normalised input (numpy or tensor) -> exp-scores [C,h,w] on the device."""
@@ -173,6 +236,7 @@ class Evaluator(object):
         H, W = img_d.shape[0], img_d.shape[1]
         sh, sw, pad_rows, pad_cols, margin, wins, raw_pad = self._windows(img_d, s, crop_size, stride_rate)
         data = None
+        fused = None                              # TSG_INFER=1: the score map of the fused tail, [C, sh, sw]
         for i0 in range(0, len(wins), self.window_batch):
             chunk = wins[i0:i0 + self.window_batch]
             # window origin in PADDED coordinates -> position in the scaled image; a padded dimension has one window at 0,
@@ -181,11 +245,22 @@ class Evaluator(object):
                               max(sx - margin[2], 0) if sw >= crop_size else 0] for sy, sx in chunk], dtype=np.int32)
             x, _ = kp.augment_crop([img_d] * len(chunk), None, geom, (crop_size, crop_size), self.image_mean, self.image_std,
                                    pad_pixel=0.0 if raw_pad else -1.0, inv_scale=np.full((len(chunk), 2), float(s)))
+            if _tsg_infer() and fused is not False:
+                r = self._fused_window_scores(x, fused, tail_geometry(chunk, margin, sh, sw, crop_size), crop_size,
+                                              (sh, sw))
+                if r is not None:
+                    fused = r
+                    continue
+                if fused is not None:
+                    raise RuntimeError("TSG_INFER: the network's output changed kind between window batches")
+                fused = False
             t = self._network_scores(x)
             if data is None:
                 data = torch.zeros((t.shape[1], pad_rows, pad_cols), dtype=torch.float32, device=t.device)
             for (sy, sx), tt in zip(chunk, t):
                 data[:, sy:sy + crop_size, sx:sx + crop_size] += tt
+        if fused is not None and fused is not False:
+            return fused
         return data[:, margin[0]:pad_rows - margin[1], margin[2]:pad_cols - margin[3]].contiguous()
 
     def scale_process(self, img, ori_shape, crop_size, stride_rate, device=None, scale=1.0):

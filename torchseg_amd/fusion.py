@@ -99,12 +99,17 @@ def materialize(v):
 class DeferredLogSoftmax(_Deferred):
     """F.log_softmax(x, dim=1) of a [B,C,H,W] tensor (or of a pending up-sampling of one), pending."""
 
-    def __init__(self, x):
+    def __init__(self, x, tail=False):
         self.x = x
+        self.tail = tail             # inference (FuseMode(infer=True), no grad) over a pending up-sampling: one fused pass
 
     def materialize(self):
         if self._value is None:
             from .upsample import DeferredUpsample
+            if self.tail:
+                # log_softmax(interpolate(z)) in fp32 straight from the logits' taps (tsg_seg_tail_logprob)
+                self._value = K.provider().seg_tail_logprob(self.x.z.contiguous(), *self.x.out_hw)
+                return self._value
             x = self.x.materialize() if isinstance(self.x, DeferredUpsample) else self.x
             self._value = torch._log_softmax(x, 1, False) if x.dtype == torch.float32 else torch.log_softmax(x, 1)
         return self._value
@@ -399,7 +404,8 @@ def _mutates(func, kwargs):
 # counts say whether the fused path is actually taken
 stats = {"iadd_deferred": 0, "iadd_declined_alias": 0, "iadd_declined_not_augmented": 0, "presum_fused": 0,
          "materialized_before_mutation": 0, "head_deferred": 0, "ce_fused": 0, "psa_deferred": 0,
-         "cbr_deferred": 0, "cbr_fed": 0, "cbr_stem_fused": 0, "cbr_materialized": 0, "forked": 0}
+         "cbr_deferred": 0, "cbr_fed": 0, "cbr_stem_fused": 0, "cbr_materialized": 0, "forked": 0,
+         "tail_deferred": 0}
 
 
 _LOG_SOFTMAX_FUNCS = (F.log_softmax, torch.log_softmax, torch.Tensor.log_softmax)
@@ -444,9 +450,10 @@ class FuseMode(TorchFunctionMode):
     allocations inside our own kernel wrappers included), so the first thing it does is one set lookup that sends
     everything it has no business with straight on."""
 
-    def __init__(self, psa=False, loss=True, add_up=True, head=False, chain=False):
+    def __init__(self, psa=False, loss=True, add_up=True, head=False, chain=False, infer=False):
         super().__init__()
         self.psa, self.loss, self.add_up, self.head = bool(psa), bool(loss), bool(add_up), bool(head)
+        self.infer = bool(infer)     # torchseg_amd.infer: under no_grad the head's up-sampling and log_softmax stay pending
         self.chain = bool(chain)
         self._pending = []           # weak references to DeferredSums that have not been used yet
         self._cbrs = []              # PendingCbrs handed out (settled at exit: a BatchNorm must not be skipped)
@@ -461,6 +468,9 @@ class FuseMode(TorchFunctionMode):
         if self.add_up:
             watch.update(_IADD_FUNCS)
         if self.add_up or self.head:
+            watch.add(F.interpolate)
+        if self.infer:
+            watch.update(_LOG_SOFTMAX_FUNCS)
             watch.add(F.interpolate)
         self._watch = frozenset(watch)
 
@@ -551,6 +561,12 @@ class FuseMode(TorchFunctionMode):
                 if dim == 1 and a.dim() == 3 and a.is_cuda and kwargs.get("dtype") is None and a.dtype in _FLOATS:
                     stats["psa_deferred"] += 1
                     return _DeferredColSoftmax(a)
+        if self.infer and func in _LOG_SOFTMAX_FUNCS and args and not torch.is_grad_enabled():
+            from .upsample import DeferredUpsample
+            dim = kwargs.get("dim", args[1] if len(args) > 1 else None)
+            if isinstance(args[0], DeferredUpsample) and dim == 1 and kwargs.get("dtype") is None:
+                stats["tail_deferred"] += 1
+                return DeferredLogSoftmax(args[0], tail=True)
         if self.loss:
             if func in _LOG_SOFTMAX_FUNCS and args and _is_logits(args[0]) and torch.is_grad_enabled() \
                     and args[0].requires_grad:
@@ -590,8 +606,10 @@ class FuseMode(TorchFunctionMode):
                         and (size is not None or scale is not None) and not kwargs.get("antialias", False):
                     stats["presum_fused"] += 1
                     return upsample_presum(s.a, s.b, size=size, scale_factor=scale)
-        if self.head and func is F.interpolate and args and _is_map(args[0]) and torch.is_grad_enabled() \
-                and args[0].requires_grad and kwargs.get("mode") == "bilinear" and kwargs.get("align_corners") \
+        if (self.head or self.infer) and func is F.interpolate and args and _is_map(args[0]) \
+                and ((self.head and torch.is_grad_enabled() and args[0].requires_grad)
+                     or (self.infer and not torch.is_grad_enabled())) \
+                and kwargs.get("mode") == "bilinear" and kwargs.get("align_corners") \
                 and not kwargs.get("antialias", False):
             # the last statement of a head: logits up-sampled by >= 4 for the criterion.  Returned pending: our
             # criteria evaluate the interpolation inside their kernels (tsg_ohem_up_*), anything else materialises it

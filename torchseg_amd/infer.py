@@ -1,0 +1,103 @@
+"""Inference wrapper: a trained network on our kernels for evaluation and timing.
+
+`prepare_inference(network)` returns a module with the network's call signature, in eval mode and without gradients:
+  - nn.BatchNorm2d layers become our SyncBatchNorm (eval mode: the running-statistics apply path);
+  - the layers are re-classed onto our kernels exactly as the DDP wrapper does it (ddp.install_kernels);
+  - forward runs under bf16 autocast (TSG_DTYPE=fp32: the fp32 parity mode, exact convolutions) and FuseMode with
+    `infer=True`: under no_grad the head's `F.interpolate(logits, bilinear, align_corners=True)` and the
+    `F.log_softmax(., dim=1)` after it stay pending (fusion.DeferredLogSoftmax(tail=True)).  The Evaluator consumes that
+    value without materialising it (tsg_seg_tail_accum); any other use materialises it through tsg_seg_tail_logprob, so
+    the value is what the network returns;
+  - graph=True: the forward is captured once per input shape and dtype (one hipGraph on the capturing stream, no side
+    streams: TSG_FORK_MODULES is not applied here) and replayed from a static input buffer.  The returned tensor is that
+    graph's static output: it is overwritten by the next call with the same shape.
+The `+=` / interpolate pre-sum and the ConvBnRelu chain fusions stay gated on autograd as in training (not enabled here).
+"""
+import contextlib
+import os
+
+import torch
+import torch.nn as nn
+
+
+def _compute_dtype(dtype):
+    if dtype is not None:
+        return dtype
+    name = os.environ.get("TSG_DTYPE", "bf16").lower()
+    return {"bf16": torch.bfloat16, "bfloat16": torch.bfloat16, "fp32": torch.float32, "float32": torch.float32}[name]
+
+
+class InferenceModule(nn.Module):
+    def __init__(self, network, dtype=None, channels_last=None, graph=False):
+        super().__init__()
+        from . import ddp
+        from .syncbn import convert_syncbn_model
+        first = next(network.parameters(), None)
+        if first is None or not first.is_cuda:
+            raise RuntimeError("prepare_inference: move the network to the GPU first (there is no CPU path)")
+        network = convert_syncbn_model(network)
+        network.eval()
+        for p in network.parameters():
+            p.requires_grad_(False)
+        self.module = network
+        self.compute_dtype = _compute_dtype(dtype)
+        if channels_last is None:
+            channels_last = ddp._env_flag("TSG_CHANNELS_LAST", True)
+        self.channels_last = bool(channels_last)
+        if self.channels_last:
+            ddp.apply_channels_last(self.module)
+            from . import syncbn
+            syncbn.PREFER_CHANNELS_LAST_OUTPUT = True
+        from .upsample import install_aten_overrides
+        install_aten_overrides()
+        ddp.install_kernels(self.module, self.compute_dtype)
+        self.graph = bool(graph)
+        self._graphs = {}
+
+    def train(self, mode=True):
+        return super().train(False)              # an inference module stays in eval mode
+
+    def _eager(self, *inputs, **kwargs):
+        from .fusion import FuseMode
+        with contextlib.ExitStack() as stack:
+            stack.enter_context(torch.no_grad())
+            if self.compute_dtype != torch.float32:
+                stack.enter_context(torch.autocast("cuda", dtype=self.compute_dtype))
+            stack.enter_context(FuseMode(loss=False, add_up=False, head=False, chain=False, infer=True))
+            return self.module(*inputs, **kwargs)
+
+    def forward(self, *inputs, **kwargs):
+        if not self.graph or kwargs or len(inputs) != 1 or not isinstance(inputs[0], torch.Tensor):
+            return self._eager(*inputs, **kwargs)
+        from .fusion import materialize
+        x = inputs[0]
+        key = (tuple(x.shape), x.dtype, x.device)
+        entry = self._graphs.get(key)
+        if entry is None:
+            static_in = x.clone()
+            with torch.no_grad():
+                materialize(self._eager(static_in))          # warm-up: allocations, lazy installs, kernel selection
+            torch.cuda.current_stream().synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                static_out = materialize(self._eager(static_in))
+            entry = self._graphs[key] = (g, static_in, static_out)
+        g, static_in, static_out = entry
+        static_in.copy_(x)
+        g.replay()
+        return static_out
+
+
+def prepare_inference(network, dtype=None, channels_last=None, graph=False):
+    """See the module docstring.  `dtype`: torch.bfloat16 or torch.float32 (default: TSG_DTYPE, bf16)."""
+    if isinstance(network, InferenceModule):
+        return network
+    return InferenceModule(network, dtype=dtype, channels_last=channels_last, graph=graph)
+
+
+def pending_tail(out):
+    """(z, (H, W)) when `out` is the pending log_softmax of an up-sampled head, else None."""
+    from .fusion import DeferredLogSoftmax
+    if isinstance(out, DeferredLogSoftmax) and out.tail and out._value is None:
+        return out.x.z.contiguous(), out.x.out_hw
+    return None

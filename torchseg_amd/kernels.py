@@ -1258,6 +1258,58 @@ class HipKernels:
                                                 int(accumulate), L.stream_ptr(x)), "tsg_resize_bilinear_hp")
         return out
 
+    # ---- segmentation head tail (evaluation) -----------------------------------
+    def seg_tail_logprob(self, z, H, W, out=None):
+        """z [N,C,h,w] f32 / bf16 contiguous -> fp32 [N,C,H,W] = log_softmax(interpolate(z, (H,W), bilinear,
+        align_corners=True), 1), the interpolated logit formed in fp32 from the taps"""
+        _require_contiguous(z)
+        N, Cc, h, w = z.shape
+        dt = L.dtype_code(z)
+        if not self.lib.tsg_seg_tail_logprob_supported(dt, Cc, h, w, int(H), int(W)):
+            raise L.TsgError(f"seg_tail_logprob: unsupported shape {tuple(z.shape)} -> ({H}, {W})")
+        if out is None:
+            out = torch.empty((N, Cc, int(H), int(W)), dtype=torch.float32, device=z.device)
+        L.check(self.lib.tsg_seg_tail_logprob(z.data_ptr(), dt, N, Cc, h, w, int(H), int(W), out.data_ptr(),
+                                              L.stream_ptr(z)), "tsg_seg_tail_logprob")
+        return out
+
+    def seg_tail_accum(self, z, zflip, geom, dst, H, W, accumulate=True, region=None):
+        """dst [C,Hd,Wd] fp32 (+)= exp(lp + flip(lp_flip)) of every window n of z [N,C,h,w] (zflip: the logits of the
+        mirrored input, or None), lp = log_softmax(interpolate(z, (H,W))); geom [N,6] = (oy, ox, t, l, rows, cols)
+        (tsg_seg_tail_accum).  geom: host int array (uploaded here; the region is its union), or an int32 device
+        tensor with `region` = (by0, by1, bx0, bx1) given (graph capture: nothing is uploaded)."""
+        _require_contiguous(z, zflip, dst)
+        N, Cc, h, w = z.shape
+        if zflip is not None and (zflip.shape != z.shape or zflip.dtype != z.dtype):
+            raise L.TsgError("seg_tail_accum: zflip must match z")
+        if dst.dtype != torch.float32 or dst.dim() != 3 or dst.shape[0] != Cc:
+            raise L.TsgError("seg_tail_accum: dst must be fp32 [C, Hd, Wd]")
+        Hd, Wd = dst.shape[1], dst.shape[2]
+        dt = L.dtype_code(z)
+        if not self.lib.tsg_seg_tail_accum_supported(dt, Cc, h, w, int(H), int(W), Hd, Wd):
+            raise L.TsgError(f"seg_tail_accum: unsupported shape {tuple(z.shape)} -> ({H}, {W}) into {tuple(dst.shape)}")
+        if isinstance(geom, torch.Tensor) and geom.is_cuda:
+            if region is None or geom.dtype != torch.int32 or tuple(geom.shape) != (N, 6) or not geom.is_contiguous():
+                raise L.TsgError("seg_tail_accum: a device geom is int32 [N,6] and needs `region`")
+            g_dev = geom
+        else:
+            import numpy as np
+            g = np.asarray(geom, dtype=np.int64).reshape(N, 6)
+            oy, ox, t, l, rows, cols = (g[:, i] for i in range(6))
+            if ((rows < 0) | (cols < 0) | (oy < 0) | (ox < 0) | (t < 0) | (l < 0) | (t + rows > H) | (l + cols > W)
+                    | (oy + rows > Hd) | (ox + cols > Wd)).any():
+                raise L.TsgError(f"seg_tail_accum: window geometry out of range: {g.tolist()}")
+            live = (rows > 0) & (cols > 0)
+            if region is None:
+                region = ((int(oy[live].min()), int((oy + rows)[live].max()), int(ox[live].min()),
+                           int((ox + cols)[live].max())) if live.any() else (0, 0, 0, 0))
+            g_dev = torch.from_numpy(g.astype(np.int32)).to(z.device)
+        by0, by1, bx0, bx1 = (int(v) for v in region)
+        L.check(self.lib.tsg_seg_tail_accum(z.data_ptr(), L.ptr(zflip), dt, N, Cc, h, w, int(H), int(W), g_dev.data_ptr(),
+                                            dst.data_ptr(), Hd, Wd, by0, by1, bx0, bx1, int(bool(accumulate)),
+                                            L.stream_ptr(z)), "tsg_seg_tail_accum")
+        return dst
+
     # ---- evaluation metric ----------------------------------------------------
     def confusion_map(self, pred, gt, n_cl, out=None):
         """pred, gt: class-index maps (int64 or uint8, same numel) -> int64 [n_cl*n_cl + 3], accumulated into `out`"""
