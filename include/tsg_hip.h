@@ -251,6 +251,18 @@ int tsg_stem_conv_fwd(const void* x, const float* w, void* y, int64_t B, int64_t
                       void* ws, size_t ws_bytes, void* stream);
 int tsg_stem_conv_wrw(const void* x, const void* dy, float* dw, int64_t B, int64_t H, int64_t W,
                       void* ws, size_t ws_bytes, void* stream);
+/* Deep-stem image convolution — replaces the vendor call behind nn.Conv2d(3, 64, kernel_size=3, stride=2, padding=1,
+ * bias=False), the first layer of the ResNet-v1c deep stem (furnace/base_model/resnet.py:111, deep_stem=True).  The
+ * same contract as tsg_stem_conv_*: x [B,3,H,W] bf16 NCHW (any H, W); y and dy [B,OH,OW,64] bf16 channels_last,
+ * OH = (H-1)/2+1; w and dw fp32 [64,3,3,3] (rounded to bf16 for the MFMA as autocast does; fp32 accumulation; dw folded
+ * from per-block partials in a fixed order, no atomics).  ws: tsg_stem3_conv_ws_bytes() bytes, 16-B aligned. */
+int tsg_stem3_conv_supported(int dtype, int Cin, int Cout, int kh, int kw, int stride, int pad,
+                             int dilation, int groups, int64_t H, int64_t W);
+size_t tsg_stem3_conv_ws_bytes(void);
+int tsg_stem3_conv_fwd(const void* x, const float* w, void* y, int64_t B, int64_t H, int64_t W,
+                       void* ws, size_t ws_bytes, void* stream);
+int tsg_stem3_conv_wrw(const void* x, const void* dy, float* dw, int64_t B, int64_t H, int64_t W,
+                       void* ws, size_t ws_bytes, void* stream);
 /* The weight gradient with the BatchNorm + ReLU backward of the layer behind the stem folded into its staging: instead
  * of dy it takes da (gradient w.r.t. relu(bn(xc))), the stem's own output xc and the backward pack bp[5][64] of
  * tsg_bn_bwd_coeffs, and evaluates dy = a dv + Bc (xc - mean) + C2, dv = [a xc + b > 0] da (tsg_bn_bwd_apply's

@@ -370,7 +370,7 @@ def _broadcast_coalesced(tensors, src, group):
 
 def install_kernels(module, compute_dtype):
     """Re-class the network's layers onto our kernels (GPU only), in the order the DDP wrapper has always applied them:
-    split bias, stem, depthwise, 3x3 conv, adaptive pool, classifier, pooled 1x1, pointwise 1x1, and in fp32 (the parity
+    split bias, stem, deep stem (opt-in), depthwise, 3x3 conv, adaptive pool, classifier, pooled 1x1, pointwise 1x1, and in fp32 (the parity
     mode) the exact convolutions.  Shared by DistributedDataParallel and torchseg_amd.infer.prepare_inference."""
     if _env_flag("TSG_SPLIT_BIAS", True):
         from .convbias import split_conv_bias
@@ -378,6 +378,9 @@ def install_kernels(module, compute_dtype):
     if _env_flag("TSG_STEM_CONV", True):
         from .stemconv import install_stem_conv
         install_stem_conv(module)
+    if _env_flag("TSG_DEEP_STEM_CONV", False):
+        from .stemconv import install_deep_stem_conv
+        install_deep_stem_conv(module)                  # v1c deep stem's 3x3/2 image convolution: opt-in (default 0)
     if _env_flag("TSG_DW_CONV", True):
         from .dwconv import install_depthwise_conv
         install_depthwise_conv(module)                  # depthwise 3x3 layers (Xception39): ours, reproducible

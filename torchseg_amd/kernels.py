@@ -450,6 +450,39 @@ class HipKernels:
                                            ws.numel(), L.stream_ptr(x)), "tsg_stem_conv_wrw")
         return dw
 
+    # ---- deep-stem image convolution (3x3 / s2 / p1, 3 -> 64) ------------------
+    def stem3_conv_supported(self, x, weight, stride, padding, dilation, groups):
+        if x.dim() != 4 or weight.dim() != 4 or x.dtype != torch.bfloat16 or not x.is_contiguous():
+            return False
+        return bool(self.lib.tsg_stem3_conv_supported(L.dtype_code(x), x.shape[1], weight.shape[0], weight.shape[2],
+                                                      weight.shape[3], stride, padding, dilation, groups,
+                                                      x.shape[2], x.shape[3]))
+
+    def stem3_conv_fwd(self, x, weight):
+        """x [B,3,H,W] bf16 contiguous, weight fp32 [64,3,3,3] -> y [B,64,OH,OW] bf16 channels_last"""
+        _require_contiguous(x, weight)
+        B, _, H, W = x.shape
+        y = torch.empty((B, 64, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=x.dtype, device=x.device,
+                        memory_format=torch.channels_last)
+        ws = self._scratch("stem3", self.lib.tsg_stem3_conv_ws_bytes(), x.device)
+        L.check(self.lib.tsg_stem3_conv_fwd(x.data_ptr(), weight.data_ptr(), y.data_ptr(), B, H, W, ws.data_ptr(),
+                                            ws.numel(), L.stream_ptr(x)), "tsg_stem3_conv_fwd")
+        return y
+
+    def stem3_conv_wrw(self, x, dy):
+        """x as in stem3_conv_fwd, dy [B,64,OH,OW] bf16 channels_last -> dw fp32 [64,3,3,3]"""
+        _require_contiguous(x)
+        if dy.dtype != torch.bfloat16 or not dy.is_contiguous(memory_format=torch.channels_last):
+            raise ValueError("stem3_conv_wrw expects a bf16 channels_last gradient")
+        B, _, H, W = x.shape
+        if tuple(dy.shape) != (B, 64, (H - 1) // 2 + 1, (W - 1) // 2 + 1):
+            raise ValueError("stem3_conv_wrw: gradient shape %s does not match the image %s" % (tuple(dy.shape), tuple(x.shape)))
+        dw = torch.empty((64, 3, 3, 3), dtype=torch.float32, device=x.device)
+        ws = self._scratch("stem3", self.lib.tsg_stem3_conv_ws_bytes(), x.device)
+        L.check(self.lib.tsg_stem3_conv_wrw(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, H, W, ws.data_ptr(),
+                                            ws.numel(), L.stream_ptr(x)), "tsg_stem3_conv_wrw")
+        return dw
+
     def stem_conv_wrw_bn(self, x, da, xc, bp):
         """stem_conv_wrw of dy = BN+ReLU backward(da; xc, bp) without writing dy: x the image (as stem_conv_fwd), da / xc
         [B,64,OH,OW] bf16 channels_last (gradient w.r.t. relu(bn(xc)) / the stem output), bp fp32 [5,64] backward pack"""
@@ -1437,6 +1470,8 @@ _ALGO_BYTES = {
     "bn_relu_pool_bwd_reduce": lambda a, r: _nbytes(a[0]) + _nbytes(a[1]) + _nbytes(a[2]),
     "bn_relu_pool_bwd_apply": lambda a, r: _nbytes(a[0]) + _nbytes(a[1]) + 2 * _nbytes(a[2]),
     "stem_conv_wrw": lambda a, r: _nbytes(a[0]) + _nbytes(a[1]),
+    "stem3_conv_fwd": lambda a, r: _nbytes(a[0]) + _nbytes(r),
+    "stem3_conv_wrw": lambda a, r: _nbytes(a[0]) + _nbytes(a[1]),
     "stem_conv_wrw_bn": lambda a, r: _nbytes(a[0]) + _nbytes(a[1]) + _nbytes(a[2]),
     # the recomputing stem (round 6): the image, the pooled side arrays; y is never in memory
     "stem_conv_stats": lambda a, r: _nbytes(a[0]),
@@ -1463,6 +1498,8 @@ _ALGO_FLOPS = {
     "conv3x3_s2_dgrad": lambda a, r: 2 * 9 * a[1].shape[1] * a[0].numel(),
     "stem_conv_fwd_stats": lambda a, r: 2 * 147 * r.numel(),
     "stem_conv_wrw": lambda a, r: 2 * 147 * a[1].numel(),
+    "stem3_conv_fwd": lambda a, r: 2 * 27 * r.numel(),
+    "stem3_conv_wrw": lambda a, r: 2 * 27 * a[1].numel(),
     "stem_conv_wrw_bn": lambda a, r: 2 * 147 * a[1].numel(),
     # y elements = 64 x OH x OW per image; the weight gradient evaluates the convolution AND its gradient product
     "stem_conv_stats": lambda a, r: 2 * 147 * _stem_y_numel(a[0]),
@@ -1605,7 +1642,8 @@ class KernelTimer:
         "conv3x3_fwd_dgrad": ("conv3x3_gen_fwd", "conv3x3_c64_fwd", "conv3x3_c64_s2_dgrad", "conv3x3_s2_dgrad"),
         "fused_heads": ("ohem_up_fwd", "ohem_up_bwd", "ohem_fwd", "ohem_bwd"),
         "stem": ("stem_conv_fwd", "stem_conv_fwd_stats", "stem_conv_wrw", "stem_conv_wrw_bn", "stem_conv_stats",
-                 "stem_conv_bn_relu_pool_fwd", "stem_conv_bn_relu_pool_bwd_reduce", "stem_conv_wrw_bn_pool"),
+                 "stem_conv_bn_relu_pool_fwd", "stem_conv_bn_relu_pool_bwd_reduce", "stem_conv_wrw_bn_pool",
+                 "stem3_conv_fwd", "stem3_conv_wrw"),
         "upsample": ("upsample_fwd", "upsample_presum_fwd", "upsample_bwd", "upsample_fwd_nhwc", "upsample_bwd_nhwc"),
     }
 

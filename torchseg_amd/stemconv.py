@@ -116,3 +116,57 @@ def install_stem_conv(module):
             m.__class__ = StemConv2d
             n += 1
     return n
+
+
+# ---------------------------------------------------------------- the ResNet-v1c deep stem's first convolution
+# nn.Conv2d(3, 64, 3, stride=2, padding=1, bias=False): furnace/base_model/resnet.py:111, ResNet._stem c[0], built by
+# every deep_stem=True model (FCN, PSPNet, PSANet, DFN, BiSeNet-R101).  Same contract as the 7x7 stem: the image needs no
+# gradient, so the step is tsg_stem3_conv_fwd + tsg_stem3_conv_wrw; y leaves channels_last for the BN -> ReLU -> 64->64
+# chain behind it.  Opt-in (TSG_DEEP_STEM_CONV=1, ddp.install_kernels) until an A/B on those families flips it.
+
+class _DeepStemConvFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight):
+        y = K.provider().stem3_conv_fwd(x, weight)
+        ctx.save_for_backward(x)
+        ctx.wdtype = weight.dtype
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        if dy.dtype != torch.bfloat16:
+            dy = dy.to(torch.bfloat16)
+        dy = dy.contiguous(memory_format=torch.channels_last)
+        return None, K.provider().stem3_conv_wrw(x, dy).to(ctx.wdtype)
+
+
+class DeepStemConv2d(nn.Conv2d):
+    """nn.Conv2d(3, 64, 3, 2, 1, bias=False) on tsg_stem3_conv_*: the same parameter and state-dict key.  Anything the
+    kernel does not take (fp32 compute, an input that requires grad, a CPU tensor, other hyper-parameters) runs the
+    stock forward; in the fp32 parity mode exactconv wraps this class like any other convolution."""
+
+    def forward(self, x):
+        if (x.is_cuda and self.bias is None and not x.requires_grad and self.weight.dtype == torch.float32
+                and self.padding_mode == "zeros" and x.dim() == 4 and _wants_bf16(x)):
+            xb = _as_bf16_image(x)
+            w = self.weight if self.weight.is_contiguous() else self.weight.contiguous()
+            if K.provider().stem3_conv_supported(xb, w, self.stride[0], self.padding[0], self.dilation[0], self.groups):
+                return _DeepStemConvFn.apply(xb, w)
+        return super().forward(x)
+
+
+def _is_deep_stem(m):
+    return (type(m) is nn.Conv2d and m.in_channels == 3 and m.out_channels == 64 and m.kernel_size == (3, 3)
+            and m.stride == (2, 2) and m.padding == (1, 1) and m.dilation == (1, 1) and m.groups == 1
+            and m.bias is None and m.padding_mode == "zeros")
+
+
+def install_deep_stem_conv(module):
+    """Re-class the 3x3/2 image convolutions of v1c deep stems (in place); returns how many were found."""
+    n = 0
+    for m in module.modules():
+        if _is_deep_stem(m):
+            m.__class__ = DeepStemConv2d
+            n += 1
+    return n
