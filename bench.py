@@ -18,6 +18,12 @@ display.  Inputs are resident in HBM before the timed region.  --scaling weak
 (default): every rank keeps batch 16.  --scaling strong: the reference's own setting, a
 GLOBAL batch of 16 split over the ranks (dataloader.py:51-53 batch_size // world_size,
 min_kept scaled with it, train.py:48-49).  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline figure needs: set-up, warm-up (its last steps instrumented per kernel, the
+capture and the launch-mode probe), the K timed steps, --dump-outputs, the JSON line.  --full also runs, after the
+timed region, the records that take runs of their own: the eager step and its bracketed kernel behind a replayed timed
+region, int64 labels, the reference's unchanged network, the fp32 parity mode, the OHEM k-th-branch and PSA probes,
+the N > 1 code path on one rank and the CPU baselines.  Both print the same `metric`, `value`, `ms_per_step`.
 """
 import argparse
 import contextlib
@@ -856,7 +862,7 @@ def launch_check(world, rank, args=None):
     return 0 if ok else 1
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)       # >= 20 warm-up + >= 50 timed steps
@@ -868,13 +874,18 @@ def main():
     ap.add_argument("--labels", default=None, choices=["u8", "i64"],
                     help="label dtype on the device: u8 (what the GPU loader emits; default for the ignore-255 families) "
                          "or i64 (what the reference's DataLoader hands over)")
-    ap.add_argument("--no-ohem-probe", action="store_true", help="skip the k-th-branch head record (bisenet only)")
-    ap.add_argument("--no-psa-probe", action="store_true", help="skip the PSA attention record (SURVEY 8 row a9)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the records that take runs of their own (each subject to its option "
+                         "below): eager_steps and roofline.timed_region behind a replayed timed region, labels_i64, "
+                         "reference_network, fp32_mode, ohem_kth_branch, psa_probe, forced_collectives, cpu_baseline.  Off by "
+                         "default: a plain run sets up, warms up, times --steps steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--no-ohem-probe", action="store_true", help="--full: skip the k-th-branch head record (bisenet only)")
+    ap.add_argument("--no-psa-probe", action="store_true", help="--full: skip the PSA attention record (SURVEY 8 row a9)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: the config's batch on EVERY rank (default); strong: the config's batch is the GLOBAL batch, "
                          "split over the ranks as the reference does (dataloader.py:51-53; min_kept follows, train.py:48-49)")
     ap.add_argument("--i64-steps", type=int, default=10,
-                    help="after the timed region, time this many extra steps with int64 labels (what the reference's "
+                    help="--full: after the timed region, time this many extra steps with int64 labels (what the reference's "
                          "DataLoader hands over) and report them beside the uint8 default; 0 = skip")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--network", default="native", choices=["native", "reference"],
@@ -882,14 +893,14 @@ def main():
                          "operators directly); reference: the reference's UNCHANGED model/<family>/<experiment>/network.py "
                          "(staged by tools/stage_reference.py), fused through fusion.FuseMode behind our DDP wrapper")
     ap.add_argument("--ref-steps", type=int, default=20,
-                    help="after the timed region of the native network, time this many steps of the reference's unchanged "
+                    help="--full: after the timed region of the native network, time this many steps of the reference's unchanged "
                          "network.py (same shape, same seed) and report them as config.reference_network; 0 = skip")
     ap.add_argument("--fp32-steps", type=int, default=3,
-                    help="after the timed region, time this many steps in the fp32 parity mode (exact convolutions, fp64 "
+                    help="--full: after the timed region, time this many steps in the fp32 parity mode (exact convolutions, fp64 "
                          "BatchNorm statistics: the kernels the 1e-4 parity claim is made with) -> fp32_mode; 0 = skip")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline (and the oracle checks of the probes)")
     ap.add_argument("--cpu-headline", type=int, default=1,
-                    help="also time ONE CPU step at the headline 1024x1024 shape (batch 2; about a minute of host time)")
+                    help="--full: also time ONE CPU step at the headline 1024x1024 shape (batch 2; about a minute of host time)")
     ap.add_argument("--launch-check", action="store_true", help="rendezvous of --gpus N ranks only, no GPU work (CPU-testable)")
     ap.add_argument("--graph", type=int, default=int(os.environ.get("TSG_GRAPH", "-1")),
                     help="0: eager step; 1: replay zero_grad+forward+backward from a hipGraph, optimizer eager after each "
@@ -901,7 +912,7 @@ def main():
                     help="with the default --graph (-1) on one GPU: time this many replayed and this many eagerly launched steps "
                          "after the capture and run the timed region in the faster mode (config.mode_probe); 0 = always replay")
     ap.add_argument("--forced-steps", type=int, default=20,
-                    help="after everything else (rank 0, N = 1): time this many steps of the N > 1 CODE PATH on one rank "
+                    help="--full: after everything else (rank 0, N = 1): time this many steps of the N > 1 CODE PATH on one rank "
                          "(TSG_FORCE_COLLECTIVES=1 in a process of its own: SyncBN exchanges + gradient buckets through "
                          "tsg_comm on a 1-rank RCCL group) -> config.forced_collectives; 0 = skip")
     ap.add_argument("--optimizer", default="fused", choices=["fused", "torch"])
@@ -913,7 +924,11 @@ def main():
     ap.add_argument("--miopen-find", type=int, default=int(os.environ.get("TSG_MIOPEN_FIND", "-1")),
                     help="torch.backends.cudnn.benchmark (train.py:35); 0 = immediate mode on the shipped MIOpen find-db (same "
                          "speed, 100 s faster start: the default)")
-    args = ap.parse_args()
+    return ap
+
+
+def main():
+    args = build_parser().parse_args()
     cfg = CONFIGS[args.config]
     if args.batch is None:
         args.batch = cfg["batch"]
@@ -1124,7 +1139,7 @@ def main():
         if args.dump_outputs and rank == 0:                            # before the side runs below step the model again
             dumped = dump_outputs(args.dump_outputs, model, loss)
         eager_rec = None
-        if graphed is not None:
+        if graphed is not None and args.full:
             # Replayed launches cannot be bracketed from the host.  The same step, eager, right behind the replayed region on
             # the same stream: (1) `eager_steps` = what the host costs (value / host ms beside the replayed figure), (2) the
             # dominant family's largest label bracketed with HIP events on every step of a second short run = the live
@@ -1153,7 +1168,7 @@ def main():
         # here, disclosed as config.labels).  A few extra steps with int64 labels, outside the timed region, put the other
         # figure beside it (the label width must be visibly neutral).
         i64_rec = None
-        if args.i64_steps > 0 and args.labels == "u8":
+        if args.full and args.i64_steps > 0 and args.labels == "u8":
             b64 = tuple(t.to(torch.int64) if t.dtype == torch.uint8 else t for t in batch)
             for it in range(2):
                 train_step(model, opt, b64, pol, args.warmup + args.steps + it, world)
@@ -1204,7 +1219,7 @@ def main():
     # The reference's UNCHANGED network.py: same shape, same seed, same wrapper; its fused operators
     # are reached through fusion.FuseMode instead of being called by the builder.  Timed after the headline region.
     ref_rec = None
-    if args.ref_steps > 0 and args.network == "native" and args.dtype == "bf16" and world == 1:   # rank 0 at N = 1 only, like cpu_baseline
+    if args.full and args.ref_steps > 0 and args.network == "native" and args.dtype == "bf16" and world == 1:   # rank 0 at N = 1 only, like cpu_baseline
         try:
             rmodel, ropt, _ = build_model(device, args.batch, args.size, ProbOhemCrossEntropy2d, SyncBatchNorm,
                                           seed=12345 if world == 1 else local_rank, fused_sgd=args.optimizer == "fused",
@@ -1226,7 +1241,7 @@ def main():
     # fp32 = the parity mode (the kernels the 1e-4 claim is made with: exact convolutions, fp64 BatchNorm statistics);
     # what it costs, beside the bf16 headline (VERDICT r4 missing #4)
     fp32_rec = None
-    if args.fp32_steps > 0 and args.dtype == "bf16" and world == 1:
+    if args.full and args.fp32_steps > 0 and args.dtype == "bf16" and world == 1:
         fmodel, fopt, _ = build_model(device, args.batch, args.size, ProbOhemCrossEntropy2d, SyncBatchNorm, seed=12345,
                                       fused_sgd=args.optimizer == "fused", config=args.config, focal_cls=SigmoidFocalLoss,
                                       network=args.network)
@@ -1270,7 +1285,7 @@ def main():
                        "hip_graph": bool(use_graph and replay), "hip_graph_mode": int(args.graph) if (use_graph and replay) else 0,
                        "mode_probe": mode_probe,
                        "hip_graph_fallback": graph_fallback, "eager_steps": eager_rec,
-                       "forced_collectives": None, "optimizer": args.optimizer},
+                       "forced_collectives": None, "optimizer": args.optimizer, "full": args.full},
         }
         if dumped is not None:
             out["dumped_outputs"] = dumped
@@ -1298,19 +1313,19 @@ def main():
             out["step_roofline"] = {"bound": "hbm", "algo_GB_per_img": gb_per_img,
                                     "achieved": round(per_gpu * gb_per_img, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                                     "frac": round(per_gpu * gb_per_img / HBM_PEAK_GBS, 4), "target_frac": 0.70}
-        if args.config == "bisenet" and world == 1 and not args.no_ohem_probe and args.dtype == "bf16":
+        if args.full and args.config == "bisenet" and world == 1 and not args.no_ohem_probe and args.dtype == "bf16":
             out["ohem_kth_branch"] = ohem_kth_branch_probe(device, args.batch, args.size)
             if not args.no_cpu_baseline:                   # the checker beside the device's selection (host time ~15 s)
                 try:
                     out["ohem_kth_branch"]["trained_like"]["oracle"] = ohem_kth_branch_oracle(device, args.batch, args.size)
                 except ImportError:
                     pass
-        if world == 1 and not args.no_psa_probe and args.dtype == "bf16":
+        if args.full and world == 1 and not args.no_psa_probe and args.dtype == "bf16":
             out["psa_probe"] = psa_probe(device, with_oracle=not args.no_cpu_baseline)
-        if world == 1 and not force_coll and args.forced_steps > 0:
+        if args.full and world == 1 and not force_coll and args.forced_steps > 0:
             torch.cuda.synchronize()
             out["config"]["forced_collectives"] = forced_collectives_run(args)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(headline=bool(args.cpu_headline)) if args.config == "bisenet" \
                 else cpu_baseline_family(args.config)
     if world > 1 or force_coll:

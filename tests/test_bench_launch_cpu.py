@@ -49,6 +49,19 @@ def test_defaults_follow_survey_8d():
     assert '"--steps", type=int, default=50' in src and '"--warmup", type=int, default=20' in src
 
 
+def test_full_is_off_by_default():
+    """A plain run times the headline only; the side records (CPU baselines, probes, other precisions and networks) need
+    --full, and their own options keep their defaults for it."""
+    sys.path.insert(0, ROOT)
+    import bench
+    plain = bench.build_parser().parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert plain.full is False and (plain.steps, plain.warmup) == (5, 2)
+    full = bench.build_parser().parse_args(["--full"])
+    assert full.full is True
+    assert (full.i64_steps, full.ref_steps, full.fp32_steps, full.forced_steps) == (10, 20, 3, 20)
+    assert not (full.no_cpu_baseline or full.no_ohem_probe or full.no_psa_probe)
+
+
 def test_dump_outputs_writes_the_step_results(tmp_path):
     """--dump-outputs: loss, a fixed sample of the parameters and their gradients at the same positions, the floating-point
     buffers; float32 / float64 only, the same sample positions on every call, under 64 MB."""
