@@ -286,3 +286,51 @@ def test_side_stream_tells_the_reducers_hook_from_a_foreign_one():
     h.remove()
     assert not convwrw._foreign_grad_hooks(q)
     del red
+
+
+def test_route_of_every_shipped_3x3_layer_under_every_family_switch(monkeypatch):
+    """convwrw._route is the one place that decides which kernel family serves a 3x3 layer.  The table: the layer shapes of
+    the shipped networks times the family switches, each one off in turn; the expected records were written down from the
+    expressions the host path used before they were gathered into _route (WrwConv2d._forward, _ConvWrwFn.forward,
+    bn_relu_conv, stem_bn_relu_conv), evaluated row by row.  Columns: family, stats, skip, compact, bn_on_load, dgrad_fwd."""
+    from torchseg_amd import convwrw
+    from torchseg_amd.convwrw import Route, _route, install_conv_wrw
+    shapes = [(64, 64, 1), (64, 64, 2), (64, 128, 2), (128, 128, 1), (128, 256, 2), (256, 256, 1), (256, 512, 2), (512, 512, 1)]
+    c64_s1 = Route("c64", True, True, False, True, False)
+    c64_s2 = Route("c64", True, False, False, True, False)         # conv64's stride-2 data gradient takes no addend
+    s2 = Route("s2", False, True, True, False, False)
+    gen = Route("gen", True, True, False, False, False)
+    lib_s1 = Route("lib", False, False, False, False, True)
+    lib_s2 = Route("lib", False, False, False, False, False)
+    table = {
+        None:            [c64_s1, c64_s2, s2, gen, s2, gen, s2, gen],
+        "_OWN_C64_S1":   [gen, c64_s2, s2, gen, s2, gen, s2, gen],
+        "_OWN_GEN":      [c64_s1, c64_s2, s2, lib_s1, s2, lib_s1, s2, lib_s1],
+        "_OWN_S2_DGRAD": [c64_s1, c64_s2, lib_s2, gen, lib_s2, gen, lib_s2, gen],
+        "_OWN_C64":      [gen, s2, s2, gen, s2, gen, s2, gen],
+    }
+    defaults = {"_OWN_C64": True, "_OWN_C64_S1": True, "_OWN_GEN": True, "_OWN_S2_DGRAD": True, "_C64_STATS": True,
+                "_GEN_STATS": True, "_GEN_BN_ON_LOAD": False, "_DGRAD_FWD": True, "_DGRAD_ANY": True}
+
+    def layer(cin, cout, stride):
+        conv = nn.Conv2d(cin, cout, 3, stride, 1, bias=False).to(memory_format=torch.channels_last)
+        assert install_conv_wrw(conv) == 1 and conv.training
+        return conv, torch.zeros(2, cin, 8, 8, dtype=torch.bfloat16).contiguous(memory_format=torch.channels_last)
+
+    for off, want in table.items():
+        for name, value in defaults.items():
+            monkeypatch.setattr(convwrw, name, value and name != off)
+        for shape, expected in zip(shapes, want):
+            got = _route(*layer(*shape))
+            assert got == expected, (off, shape, got)
+    # the two opt-in corners: BatchNorm on load in front of the general kernel; the stem node, which has no general-kernel
+    # form and therefore stays on conv64 where TSG_CONV_C64_S1=0 sends the plain layer to the general kernel
+    for name, value in defaults.items():
+        monkeypatch.setattr(convwrw, name, value)
+    monkeypatch.setattr(convwrw, "_GEN_BN_ON_LOAD", True)
+    assert [_route(*layer(*s)).bn_on_load for s in shapes] == [True, True, False, True, False, True, False, True]
+    monkeypatch.setattr(convwrw, "_OWN_C64_S1", False)
+    assert _route(*layer(64, 64, 1), general=False) == Route("c64", True, False, False, False, False)
+    conv, xb = layer(64, 64, 1)
+    assert _route(conv.eval(), xb).stats is False                                  # statistics are a training-mode matter
+    assert _route(nn.Conv2d(64, 64, 3, 1, 2, dilation=2, bias=False), xb) is None  # not ours: nn.Conv2d.forward runs it

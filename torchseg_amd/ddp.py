@@ -57,8 +57,10 @@ upsample overrides.  Controlled by env so train.py needs no edit:
   TSG_DW_CONV=1|0       (default 1 on GPU: depthwise 3x3 convolutions (Xception39) on tsg_dwconv3x3_*: reproducible weight
                         gradient, exact fp32 parity mode; dwconv.py)
   TSG_ADAPTIVE_POOL=1|0 (default 1 on GPU: nn.AdaptiveAvgPool2d on channels_last maps -> tsg_adaptive_avgpool_nhwc_*)
-  TSG_CONV_WRW=1|0      (default 1 on GPU: weight gradient of the 64->64 3x3/1 convolutions on tsg_conv3x3_wrw;
-                        TSG_CONV_WRW_IMPL=gen|tr|v1 picks the kernel of the 64 -> 64 layers, default gen)
+  TSG_CONV_WRW=1|0      (default 1 on GPU: the 3x3 convolutions of stride 1 / 2 with C_in, C_out multiples of 64, up to
+                        TSG_CONV_WRW_MAXC = 512, on our kernels: weight gradient on tsg_conv3x3_wrw, forward and data gradient
+                        as convwrw.py routes them; TSG_CONV_WRW_IMPL=gen|tr|v1 picks the weight-gradient kernel of the
+                        64 -> 64 stride-1 layers, default gen)
   TSG_CLS_HEAD=1|0      (default 1 on GPU: the 1x1 classifier convolution of a head (<= 32 classes) on tsg_cls_head_*:
                         planar logits for the criterion kernels, no layout copies, no separate bias passes; clshead.py)
   TSG_CONV_S2_DGRAD=1|0 (default 1 on GPU: data gradient of the stride-2 3x3 layers other than 64 -> 64 on tsg_conv3x3_s2_dgrad, the

@@ -13,9 +13,6 @@ import torch
 from . import _lib as L
 
 
-# re-exported so host modules can name layout codes as K.L.NCHW / K.L.NHWC
-
-
 def bn_layout(x):
     """(layout, N, C, HW) of a dense activation, or None if it must be copied.
 

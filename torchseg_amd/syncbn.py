@@ -172,6 +172,27 @@ def _backward_pack(kp, partial, S, C, n_local, invstd, fp, count_dev, use_batch_
     return kp.bn_bwd_coeffs(partial, S, C, float(n_local), None, use_batch_stats, invstd, fp, True, True)
 
 
+def _forward_pack(kp, x, layout, N, C, HW, mod, weight, bias, use_batch_stats, group, hint=None):
+    """What every BatchNorm forward starts with -> (invstd, fwd_pack, count_dev, world): batch statistics (`hint`: see
+    _batch_statistics) or the running estimates, folded with the affine parameters.  The order of the tensor operations
+    here is the order of kernel launches under graph capture."""
+    world = _world(group) if use_batch_stats else 1
+    gamma = weight.float() if weight is not None else None
+    beta = bias.float() if bias is not None else None
+    if use_batch_stats:
+        return _batch_statistics(kp, x, layout, N, C, HW, mod, gamma, beta, group, world, hint) + (world,)
+    mean = mod.running_mean.float()
+    invstd = torch.rsqrt(mod.running_var.float() + mod.eps)
+    return invstd, kp.bn_affine(mean, invstd, gamma, beta), None, world
+
+
+def _affine_grads(dgamma, dbeta, weight, bias):
+    """dgamma / dbeta in the dtypes of the parameters they belong to; None for a parameter the layer does not have."""
+    if weight is None:
+        return None, None
+    return dgamma.to(weight.dtype), dbeta.to(bias.dtype) if bias is not None else None
+
+
 # TSG_BN_MASKBITS=1|0 (default 1, round 6): the block tail BN -> (+identity) -> ReLU keeps its ReLU mask as one bit per
 # element (tsg_bn_apply_fwd_maskbits) and its two backward kernels read that instead of the stored output: 2 of the 8
 # tensor passes of the layer's backward gone, same values.
@@ -185,16 +206,7 @@ class _SyncBNFn(torch.autograd.Function):
         x, (layout, N, C, HW) = _dense(x)
         if residual is not None:
             residual = _like(residual, x)
-        world = _world(group) if use_batch_stats else 1
-        count_dev = None
-        gamma = weight.float() if weight is not None else None
-        beta = bias.float() if bias is not None else None
-        if use_batch_stats:
-            invstd, fp, count_dev = _batch_statistics(kp, x, layout, N, C, HW, mod, gamma, beta, group, world, hint)
-        else:
-            mean = mod.running_mean.float()
-            invstd = torch.rsqrt(mod.running_var.float() + mod.eps)
-            fp = kp.bn_affine(mean, invstd, gamma, beta)
+        invstd, fp, count_dev, world = _forward_pack(kp, x, layout, N, C, HW, mod, weight, bias, use_batch_stats, group, hint)
         mixed = (PREFER_CHANNELS_LAST_OUTPUT and residual is None and layout == K.L.NCHW
                  and kp.bn_mixed_supported(x))
         need_y = relu and residual is not None
@@ -237,11 +249,7 @@ class _SyncBNFn(torch.autograd.Function):
             dx, dres = kp.bn_bwd_apply_bits(dy, x, y, layout, N, C, HW, bp, has_res)
         else:
             dx, dres = kp.bn_bwd_apply(dy, x, y, layout, N, C, HW, bp, relu, has_res)
-        if weight is None:
-            dgamma = dbeta = None
-        else:
-            dgamma = dgamma.to(weight.dtype)
-            dbeta = dbeta.to(bias.dtype) if bias is not None else None
+        dgamma, dbeta = _affine_grads(dgamma, dbeta, weight, bias)
         return dx, dres, dgamma, dbeta, None, None, None, None, None
 
 
@@ -253,16 +261,7 @@ class _BnReluPoolFn(torch.autograd.Function):
     def forward(ctx, x, weight, bias, mod, use_batch_stats, group, hint):
         kp = K.provider()
         layout, N, C, HW = K.bn_layout(x)
-        world = _world(group) if use_batch_stats else 1
-        count_dev = None
-        gamma = weight.float() if weight is not None else None
-        beta = bias.float() if bias is not None else None
-        if use_batch_stats:
-            invstd, fp, count_dev = _batch_statistics(kp, x, layout, N, C, HW, mod, gamma, beta, group, world, hint)
-        else:
-            mean = mod.running_mean.float()
-            invstd = torch.rsqrt(mod.running_var.float() + mod.eps)
-            fp = kp.bn_affine(mean, invstd, gamma, beta)
+        invstd, fp, count_dev, world = _forward_pack(kp, x, layout, N, C, HW, mod, weight, bias, use_batch_stats, group, hint)
         y, idx = kp.bn_relu_pool_fwd(x, fp)
         ctx.save_for_backward(x, idx, weight, bias, invstd, fp, count_dev)
         ctx.cfg = (N, C, HW, use_batch_stats, group, world)
@@ -280,11 +279,7 @@ class _BnReluPoolFn(torch.autograd.Function):
         dgamma, dbeta, bp = _backward_pack(kp, partial, S, C, N * HW, invstd, fp, count_dev,
                                            use_batch_stats, group, world, x.device, parity=x.dtype == torch.float32)
         dx = kp.bn_relu_pool_bwd_apply(dpool, idx, x, bp)
-        if weight is None:
-            dgamma = dbeta = None
-        else:
-            dgamma = dgamma.to(weight.dtype)
-            dbeta = dbeta.to(bias.dtype) if bias is not None else None
+        dgamma, dbeta = _affine_grads(dgamma, dbeta, weight, bias)
         return dx, dgamma, dbeta, None, None, None, None
 
 
@@ -301,23 +296,14 @@ class _StemConvBnReluPoolFn(torch.autograd.Function):
         B, _, H, W = img.shape
         OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
         N, C, HW = B, 64, OH * OW
-        world = _world(group) if use_batch_stats else 1
-        count_dev = None
-        gamma = weight.float() if weight is not None else None
-        beta = bias.float() if bias is not None else None
-        xc = None
-        if use_batch_stats:
-            if full:
-                partial = kp.stem_conv_stats(img, w_stem)
-            else:
-                xc, partial = kp.stem_conv_fwd_stats(img, w_stem)
-            invstd, fp, count_dev = _batch_statistics(kp, img, 1, N, C, HW, mod, gamma, beta, group, world, partial)
-        else:
-            mean = mod.running_mean.float()
-            invstd = torch.rsqrt(mod.running_var.float() + mod.eps)
-            fp = kp.bn_affine(mean, invstd, gamma, beta)
-            if not full:
-                xc = kp.stem_conv_fwd(img, w_stem)
+        xc = partial = None
+        if use_batch_stats and full:
+            partial = kp.stem_conv_stats(img, w_stem)
+        elif use_batch_stats:
+            xc, partial = kp.stem_conv_fwd_stats(img, w_stem)
+        invstd, fp, count_dev, world = _forward_pack(kp, img, 1, N, C, HW, mod, weight, bias, use_batch_stats, group, partial)
+        if not (use_batch_stats or full):
+            xc = kp.stem_conv_fwd(img, w_stem)
         if full:
             y, idx = kp.stem_conv_bn_relu_pool_fwd(img, w_stem, fp)
         else:
@@ -349,11 +335,7 @@ class _StemConvBnReluPoolFn(torch.autograd.Function):
             yy = xc if _STEM_WRW_READS_Y else None
             dw = wrw_on_side_stream(lambda: kp.stem_conv_wrw_bn_pool(img, w_stem, dpool, idx, bp, xc=yy), ctx.wparam,
                                     img, dpool, idx, bp, yy)
-        if weight is None:
-            dgamma = dbeta = None
-        else:
-            dgamma = dgamma.to(weight.dtype)
-            dbeta = dbeta.to(bias.dtype) if bias is not None else None
+        dgamma, dbeta = _affine_grads(dgamma, dbeta, weight, bias)
         return None, dw, dgamma, dbeta, None, None, None, None
 
 
