@@ -451,6 +451,29 @@ int tsg_conv3x3_gen_fwd(const void* x, const void* wf, void* y, float* partial, 
                         int64_t B, int64_t H, int64_t W, int Cin, int Cout, int BN, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Dilated 3x3 / stride 1 / padding d / dilation d convolutions, d = 2 or 4 (csrc/dilconv.hip): the 3x3 layers of the
+ * dilated ResNet-v1c layer3 / layer4 behind PSPNet and PSANet.  bf16 channels_last, fp32 accumulation.
+ *   tsg_conv3x3_dil_supported: 1 exactly for bf16, 3x3, stride 1, dilation 2 or 4, pad == dilation, groups 1, C_in a
+ *     multiple of 16 and C_out a multiple of 64 (dilation 1 belongs to tsg_conv3x3_gen_*).
+ *   tsg_conv3x3_dil_fwd: x [B,H,W,Cin] -> y [B,H,W,Cout].  wf = tsg_conv3x3_gen_prep_filter(..., BN 64): mode 0 for the
+ *     forward, mode 1 (fed dy) for the data gradient.  Cout may be any multiple of 16; wf is then the filter of a
+ *     convolution with Cout rounded up to 64 (zero rows for the surplus channels, which are not stored).  partial (may
+ *     be NULL; Cout a multiple of 64): [S][2][Cout] sums / square sums of the bf16-rounded outputs, S =
+ *     tsg_conv3x3_dil_stats_partials(...).  addend (may be NULL; not together with partial): y = bf16(bf16(conv) + addend).
+ *   tsg_conv3x3_dil_wrw: dw[oc][kh][kw][ci] = sum dy[b,oh,ow,oc] x[b,oh+d(kh-1),ow+d(kw-1),ci], fp32 [Cout][3][3][Cin];
+ *     per-block partials in ws (tsg_conv3x3_dil_wrw_ws_bytes, 0 = unsupported) folded in fp64 in a fixed order: no
+ *     atomics, bit-identical from run to run.
+ * ---------------------------------------------------------------------- */
+int tsg_conv3x3_dil_supported(int dtype, int Cin, int Cout, int kh, int kw, int stride, int pad, int dilation,
+                              int groups);
+int tsg_conv3x3_dil_stats_partials(int64_t B, int64_t H, int64_t W, int Cin, int Cout, int dilation);
+int tsg_conv3x3_dil_fwd(const void* x, const void* wf, void* y, float* partial, const void* addend, int64_t B, int64_t H,
+                        int64_t W, int Cin, int Cout, int dilation, void* stream);
+size_t tsg_conv3x3_dil_wrw_ws_bytes(int64_t B, int64_t H, int64_t W, int Cin, int Cout, int dilation);
+int tsg_conv3x3_dil_wrw(const void* x, const void* dy, float* dw, int64_t B, int64_t H, int64_t W, int Cin, int Cout,
+                        int dilation, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * OHEM 2-D cross entropy — replaces ProbOhemCrossEntropy2d.forward
  * (furnace/seg_opr/loss_opr.py:68-98) and the nn.CrossEntropyLoss it ends in.
  * logits are [B, C, HW] (NCHW planar), labels [B*HW].

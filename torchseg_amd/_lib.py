@@ -98,6 +98,11 @@ _PROTOS = {
     "tsg_conv3x3_s2_dgrad": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _i, _i, _p]),
     "tsg_conv3x3_s2_dgrad_subadd": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _i, _i, _p]),
     "tsg_conv3x3_gen_fwd": (_i, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i, _i, _i, _p]),
+    "tsg_conv3x3_dil_supported": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i]),
+    "tsg_conv3x3_dil_stats_partials": (_i, [_i64, _i64, _i64, _i, _i, _i]),
+    "tsg_conv3x3_dil_fwd": (_i, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i, _i, _i, _p]),
+    "tsg_conv3x3_dil_wrw_ws_bytes": (_sz, [_i64, _i64, _i64, _i, _i, _i]),
+    "tsg_conv3x3_dil_wrw": (_i, [_p, _p, _p, _i64, _i64, _i64, _i, _i, _i, _p, _sz, _p]),
     "tsg_stem3_conv_supported": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i64, _i64]),
     "tsg_stem3_conv_ws_bytes": (_sz, []),
     "tsg_stem3_conv_fwd": (_i, [_p, _p, _p, _i64, _i64, _i64, _p, _sz, _p]),

@@ -56,6 +56,8 @@ upsample overrides.  Controlled by env so train.py needs no edit:
   TSG_STEM_CONV=1|0     (default 1 on GPU: 7x7/2 image stems on tsg_stem_conv_* instead of MIOpen)
   TSG_DW_CONV=1|0       (default 1 on GPU: depthwise 3x3 convolutions (Xception39) on tsg_dwconv3x3_*: reproducible weight
                         gradient, exact fp32 parity mode; dwconv.py)
+  TSG_CONV_DIL=0|1      (default 0: the dilated 3x3 convolutions (d = 2 / 4) of the PSPNet / PSANet backbone on tsg_conv3x3_dil_*:
+                        statistics epilogue, reproducible weight gradient on the side stream; dilconv.py)
   TSG_ADAPTIVE_POOL=1|0 (default 1 on GPU: nn.AdaptiveAvgPool2d on channels_last maps -> tsg_adaptive_avgpool_nhwc_*)
   TSG_CONV_WRW=1|0      (default 1 on GPU: the 3x3 convolutions of stride 1 / 2 with C_in, C_out multiples of 64, up to
                         TSG_CONV_WRW_MAXC = 512, on our kernels: weight gradient on tsg_conv3x3_wrw, forward and data gradient
@@ -372,7 +374,7 @@ def _broadcast_coalesced(tensors, src, group):
 
 def install_kernels(module, compute_dtype):
     """Re-class the network's layers onto our kernels (GPU only), in the order the DDP wrapper has always applied them:
-    split bias, stem, deep stem (opt-in), depthwise, 3x3 conv, adaptive pool, classifier, pooled 1x1, pointwise 1x1, and in fp32 (the parity
+    split bias, stem, deep stem (opt-in), depthwise, 3x3 conv, dilated 3x3 conv (opt-in), adaptive pool, classifier, pooled 1x1, pointwise 1x1, and in fp32 (the parity
     mode) the exact convolutions.  Shared by DistributedDataParallel and torchseg_amd.infer.prepare_inference."""
     if _env_flag("TSG_SPLIT_BIAS", True):
         from .convbias import split_conv_bias
@@ -389,6 +391,9 @@ def install_kernels(module, compute_dtype):
     if _env_flag("TSG_CONV_WRW", True):
         from .convwrw import install_conv_wrw
         install_conv_wrw(module)
+    if _env_flag("TSG_CONV_DIL", False):
+        from .dilconv import install_dilated_conv
+        install_dilated_conv(module)                    # dilated 3x3 layers (PSPNet / PSANet backbone): opt-in (default 0)
     if _env_flag("TSG_ADAPTIVE_POOL", True):
         from .pool import install_adaptive_pool
         install_adaptive_pool(module)

@@ -1102,6 +1102,77 @@ class HipKernels:
                                              L.ptr(addend), B, H, W, Cin, Cout, bn, L.stream_ptr(x)), "tsg_conv3x3_gen_fwd")
         return (y, partial) if with_stats else y
 
+    # ---- dilated 3x3 convolutions (PSPNet / PSANet backbone; csrc/dilconv.hip) ---------------
+    def conv3x3_dil_supported(self, x, weight, stride, padding, dilation, groups):
+        """3x3 / stride 1 / padding d / dilation d, d in (2, 4): bf16 channels_last, Cin % 16 == 0, Cout % 64 == 0"""
+        if x.dim() != 4 or x.dtype != torch.bfloat16 or not x.is_contiguous(memory_format=torch.channels_last):
+            return False
+        return bool(self.lib.tsg_conv3x3_dil_supported(L.dtype_code(x), x.shape[1], weight.shape[0], weight.shape[2],
+                                                       weight.shape[3], stride, padding, dilation, groups))
+
+    def conv3x3_dil_prep_filter(self, weight, mode, like):
+        """weight [O,I,3,3] (fp32 master or bf16) -> the fragment-order filter tsg_conv3x3_dil_fwd reads: mode 0 for
+        conv(x, w), mode 1 for the data gradient conv(dy, rot180(w)^T).  The layout is conv3x3_gen_prep_filter's at tile
+        width 64 (a parameter's image comes from the shadow bank); a weight that is not channels_last is cast per call, and
+        a mode-1 filter whose C_in is not a multiple of 64 is prepared with zero rows up to the next one."""
+        if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
+            raise ValueError("conv3x3_dil_prep_filter expects an [O, I, 3, 3] weight")
+        I = weight.shape[1]
+        if not weight.is_contiguous(memory_format=torch.channels_last):
+            weight = weight.detach().to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+        if mode and I % 64:
+            weight = torch.nn.functional.pad(weight.detach(), (0, 0, 0, 0, 0, -I % 64)).contiguous(memory_format=torch.channels_last)
+        return self.conv3x3_gen_prep_filter(weight, mode, like, bn=64)[0]
+
+    def conv3x3_dil_fwd(self, x, wf, Cout, dilation, with_stats=False, addend=None):
+        """x [B,Cin,H,W] bf16 channels_last, wf = conv3x3_dil_prep_filter(..., like=x) -> y [B,Cout,H,W] channels_last, or
+        (y, partial [S,2,Cout]).  addend: bf16 channels_last [B,Cout,H,W], y = bf16(bf16(conv) + addend)."""
+        if x.dim() != 4 or not x.is_contiguous(memory_format=torch.channels_last) or x.dtype != torch.bfloat16:
+            raise ValueError("conv3x3_dil_fwd expects a bf16 channels_last input")
+        B, Cin, H, W = x.shape
+        if wf.numel() != 9 * Cin * (-(-Cout // 64) * 64) or wf.dtype != torch.bfloat16:
+            raise ValueError("conv3x3_dil_fwd: the prepared filter does not belong to this convolution")
+        y = torch.empty((B, Cout, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+        if addend is not None and (with_stats or addend.shape != y.shape or addend.dtype != y.dtype
+                                   or not addend.is_contiguous(memory_format=torch.channels_last)):
+            raise ValueError("conv3x3_dil_fwd: addend must be a bf16 channels_last tensor of the output's shape (no statistics)")
+        partial = None
+        if with_stats:
+            S = self._count(("dil_stats", B, H, W, Cin, Cout, dilation),
+                            lambda: self.lib.tsg_conv3x3_dil_stats_partials(B, H, W, Cin, Cout, int(dilation)),
+                            "tsg_conv3x3_dil_stats_partials")
+            partial = torch.empty((S, 2, Cout), dtype=torch.float32, device=x.device)
+        L.check(self.lib.tsg_conv3x3_dil_fwd(x.data_ptr(), wf.data_ptr(), y.data_ptr(), L.ptr(partial), L.ptr(addend), B, H, W,
+                                             Cin, Cout, int(dilation), L.stream_ptr(x)), "tsg_conv3x3_dil_fwd")
+        return (y, partial) if with_stats else y
+
+    def conv3x3_dil_dgrad(self, dy, weight, dilation, addend=None):
+        """dy [B,Cout,H,W] bf16 channels_last, weight [Cout,Cin,3,3] -> dx [B,Cin,H,W]: the dilated forward convolution of dy
+        with the mode-1 filter (+ addend)"""
+        return self.conv3x3_dil_fwd(dy, self.conv3x3_dil_prep_filter(weight, 1, dy), weight.shape[1], dilation, addend=addend)
+
+    def conv3x3_dil_wrw(self, x, dy, dilation, out=None):
+        """x [B,Cin,H,W], dy [B,Cout,H,W] bf16 channels_last -> dw fp32 [Cout,Cin,3,3] channels_last (into `out` when given)"""
+        for t in (x, dy):
+            if t.dim() != 4 or not t.is_contiguous(memory_format=torch.channels_last) or t.dtype != torch.bfloat16:
+                raise ValueError("conv3x3_dil_wrw expects bf16 channels_last tensors")
+        B, Cin, H, W = x.shape
+        Cout = dy.shape[1]
+        if tuple(dy.shape) != (B, Cout, H, W):
+            raise ValueError("conv3x3_dil_wrw: dy does not have the output shape of a 3x3 / padding d / dilation d convolution of x")
+        if out is not None and (tuple(out.shape) != (Cout, Cin, 3, 3) or out.dtype != torch.float32
+                                or not out.is_contiguous(memory_format=torch.channels_last)):
+            raise ValueError("conv3x3_dil_wrw: out must be an fp32 channels_last [Cout, Cin, 3, 3] tensor")
+        dw = out if out is not None else \
+            torch.empty((Cout, Cin, 3, 3), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        wsb = self.lib.tsg_conv3x3_dil_wrw_ws_bytes(B, H, W, Cin, Cout, int(dilation))
+        if wsb == 0:
+            raise L.TsgError("conv3x3_dil_wrw: unsupported shape %s -> %d channels, dilation %d" % (tuple(x.shape), Cout, dilation))
+        ws = self._scratch("c3d", wsb, x.device)                  # per stream, grown to the largest layer
+        L.check(self.lib.tsg_conv3x3_dil_wrw(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, H, W, Cin, Cout, int(dilation),
+                                             ws.data_ptr(), ws.numel(), L.stream_ptr(x)), "tsg_conv3x3_dil_wrw")
+        return dw
+
     def conv3x3_s2_dgrad_supported(self, Cin, Cout):
         return bool(self.lib.tsg_conv3x3_s2_dgrad_supported(L.BF16, Cin, Cout))
 
