@@ -93,3 +93,108 @@ def test_comm_entry_points_without_gpu():
                 _lib.check(rc, "tsg_comm_get_unique_id")
         else:
             assert any(buf.raw)
+
+
+# ---- torchseg_amd/_lib.py against the header: the parser that derives _PROTOS, and the few mirrors still written by hand ----
+
+def _header():
+    src = open(os.path.join(ROOT, "include", "tsg_hip.h")).read()
+    return re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+
+
+def test_prototype_parser_on_hand_read_signatures():
+    """expected (restype, argtypes) written down from the header by hand: together they cover int, int64_t, float, double
+    and size_t by value, data / struct / handle / pointer-to-pointer parameters, and `const char*` both ways"""
+    from torchseg_amd import _lib
+    i, i64, f, d, sz, p, s = (ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double, ctypes.c_size_t,
+                              ctypes.c_void_p, ctypes.c_char_p)
+    want = {
+        "tsg_bn_finalize": (i, [p, i, i64, d, p, f, f, p, p, p, p, p, p, p, p, p]),
+        "tsg_gap_fwd": (i, [p, p, i, i, i64, i64, i64, p, sz, p]),
+        "tsg_bn_num_partials": (i, [i, i64, i64, i64]),
+        "tsg_conv3x3_gen_filter_elems": (i64, [i, i]),
+        "tsg_ohem_make_plan": (i, [i64, i, i64, f, p]),
+        "tsg_comm_create": (i, [p, i, i, i, p]),
+        "tsg_comm_error_string": (s, [i]),
+        "tsg_comm_init_library": (i, [s]),
+        "tsg_stem_conv_ws_bytes": (sz, []),
+        "tsg_augment_crop": (i, [p, p, p, p, i, i, i, p, p, f, i, p, p, i, p]),
+    }
+    for name, proto in want.items():
+        assert _lib._PROTOS[name] == proto, name
+
+
+def test_prototype_arity_equals_the_header_for_every_entry_point():
+    from torchseg_amd import _lib
+    decls = re.findall(r"\b(tsg_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", _header())
+    assert len(decls) == len(_lib._PROTOS) >= 165
+    for name, args in decls:
+        n = 0 if args.strip() in ("", "void") else args.count(",") + 1
+        assert len(_lib._PROTOS[name][1]) == n, name
+
+
+def test_prototype_parser_refuses_what_it_does_not_know():
+    import pytest
+    from torchseg_amd import _lib
+    parse = _lib._parse_protos
+    assert parse("/* int tsg_a(int x); */\n#define TSG_Z (-1)\n// int tsg_b(int x);\nsize_t tsg_y(void);\nint tsg_w();") == {
+        "tsg_y": (ctypes.c_size_t, []), "tsg_w": (ctypes.c_int, [])}
+    assert parse("const char* tsg_s(const char *a, const void* const* b, long long* c, int64_t d);") == {
+        "tsg_s": (ctypes.c_char_p, [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64])}
+    for bad in ("tsg_x(__int128 a);", "int tsg_x(__int128 a);", "int tsg_x(int a, unsigned b);", "int tsg_x(long a);",
+                "unsigned tsg_x(int a);", "int tsg_x(void (*cb)(int));"):
+        with pytest.raises(_lib.TsgError, match="tsg_x"):
+            parse(bad)
+
+
+def test_prototypes_need_neither_torch_nor_the_library():
+    import subprocess
+    import sys
+    code = ("import sys; from torchseg_amd import _lib; "
+            "assert len(_lib._PROTOS) >= 165 and _lib._lib is None and 'torch' not in sys.modules")
+    subprocess.run([sys.executable, "-c", code], cwd=ROOT, check=True, timeout=60)
+
+
+def test_ohem_plan_mirrors_the_header_struct():
+    from torchseg_amd import _lib
+    ctype = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32, "size_t": ctypes.c_size_t}
+    body = re.search(r"typedef\s+struct\s+tsg_ohem_plan\s*\{(.*?)\}\s*tsg_ohem_plan\s*;", _header(), re.S).group(1)
+    want = []
+    for decl in filter(str.strip, body.split(";")):
+        t, name, n = re.fullmatch(r"\s*(\w+)\s+(\w+)\s*(?:\[\s*(\d+)\s*\])?\s*", decl).groups()
+        want.append((name, ctype[t], int(n) if n else None))
+    got = [(name, t._type_, t._length_) if issubclass(t, ctypes.Array) else (name, t, None)
+           for name, t in _lib.OhemPlan._fields_]
+    assert len(want) == 8 and got == want
+
+
+def test_error_codes_and_enums_mirror_the_header():
+    import pytest
+    from torchseg_amd import _lib
+    src = _header()
+    codes = {k: int(v) for k, v in re.findall(r"#define\s+TSG_E_(\w+)\s+\((-\d+)\)", src)}
+    base = codes.pop("COMM_BASE")
+    assert len(codes) >= 7 and set(_lib._ERR) == set(codes.values())
+    for v in codes.values():
+        with pytest.raises(_lib.TsgError, match=re.escape("invalid argument (%s)" % _lib._ERR[v])):
+            _lib.check(v, "x")
+    # check() hands a code to RCCL's message table from TSG_E_COMM_BASE downwards, and not before
+    with pytest.raises(_lib.TsgError, match="RCCL error 0 "):
+        _lib.check(base, "x")
+    with pytest.raises(_lib.TsgError, match="RCCL error 3 "):
+        _lib.check(base - 3, "x")
+    with pytest.raises(_lib.TsgError, match="invalid argument"):
+        _lib.check(base + 1, "x")
+    enums = {k: int(v) for body in re.findall(r"enum\s*\{(.*?)\}", src, re.S) for k, v in re.findall(r"TSG_(\w+)\s*=\s*(\d+)", body)}
+    assert enums == {"F32": _lib.F32, "BF16": _lib.BF16, "NCHW": _lib.NCHW, "NHWC": _lib.NHWC, "I64": _lib.I64, "U8": _lib.U8}
+
+
+def test_call_raises_checks_error_named_after_the_entry_point():
+    import pytest
+    from torchseg_amd import _lib
+    lib = _lib.lib()
+    assert _lib.call(lib.tsg_comm_init_library, None) is None
+    with pytest.raises(_lib.TsgError, match=re.escape("tsg_conv3x3_wrw_tr: invalid argument (null pointer)")):
+        _lib.call(lib.tsg_conv3x3_wrw_tr, None, None, None, 1, 8, 8, None, 0, None)
+    with pytest.raises(_lib.TsgError, match=re.escape("tsg_comm_create: invalid argument (bad shape)")):
+        _lib.call(lib.tsg_comm_create, None, 0, 0, 0, ctypes.byref(ctypes.c_void_p()))

@@ -1,11 +1,16 @@
 """ctypes binding of libtsg_hip.so (C-ABI in include/tsg_hip.h).
 
+The header is the only place a signature is written: `_PROTOS` is parsed from it at import, so a new entry point needs
+a declaration there and nothing here.  What is still mirrored by hand (`OhemPlan`, `_ERR`, the enum constants) is
+pinned to the header by tests/test_abi.py.
+
 There is deliberately NO fallback: if the shared library is missing or a call
 returns non-zero, the caller gets an exception.  The product path never routes
 around the HIP kernels.
 """
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtsg_hip.so")
@@ -29,178 +34,48 @@ class OhemPlan(C.Structure):
                 ("ws_bytes", C.c_size_t)]
 
 
-_p, _i, _i64, _f, _d, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double, C.c_size_t
-_ip = C.POINTER(C.c_int)
+_HEADER = os.path.join(_HERE, "..", "include", "tsg_hip.h")
 
-# name -> (restype, argtypes); kept in lock-step with include/tsg_hip.h
-# (tests/test_abi.py parses the header and checks every symbol is exported).
-_PROTOS = {
-    "tsg_version": (_i, []),
-    "tsg_bn_num_partials": (_i, [_i, _i64, _i64, _i64]),
-    "tsg_bn_partial_ws_bytes": (_sz, [_i, _i64, _i64, _i64]),
-    "tsg_bn_stats": (_i, [_p, _i, _i, _i64, _i64, _i64, _p, _ip, _p]),
-    "tsg_bn_collapse": (_i, [_p, _i, _i64, _p, _p]),
-    "tsg_bn_collapse_count": (_i, [_p, _i, _i64, _p, _i64, _p]),
-    "tsg_bn_finalize": (_i, [_p, _i, _i64, _d, _p, _f, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
-    "tsg_bn_affine": (_i, [_p, _p, _p, _p, _i64, _p, _p]),
-    "tsg_bn_apply_fwd": (_i, [_p, _p, _p, _i, _i, _i64, _i64, _i64, _p, _i, _p]),
-    "tsg_bn_bwd_reduce": (_i, [_p, _p, _p, _i, _i, _i64, _i64, _i64, _p, _i, _p, _ip, _p]),
-    "tsg_bn_bwd_coeffs": (_i, [_p, _i, _i64, _d, _p, _i, _p, _p, _p, _p, _p, _p]),
-    "tsg_bn_bwd_apply": (_i, [_p, _p, _p, _p, _p, _i, _i, _i64, _i64, _i64, _p, _i, _p]),
-    "tsg_bn_maskbits_supported": (_i, [_i, _i, _i64, _i64]),
-    "tsg_bn_apply_fwd_maskbits": (_i, [_p, _p, _p, _p, _i, _i, _i64, _i64, _i64, _p, _p]),
-    "tsg_bn_bwd_reduce_maskbits": (_i, [_p, _p, _p, _i, _i, _i64, _i64, _i64, _p, _p, _p, _p]),
-    "tsg_bn_bwd_apply_maskbits": (_i, [_p, _p, _p, _p, _p, _i, _i, _i64, _i64, _i64, _p, _p]),
-    "tsg_bn_mixed_supported": (_i, [_i, _i64, _i64]),
-    "tsg_bn_mixed_num_partials": (_i, [_i64, _i64, _i64]),
-    "tsg_bn_apply_fwd_mixed": (_i, [_p, _p, _i, _i64, _i64, _i64, _p, _i, _p]),
-    "tsg_bn_bwd_reduce_mixed": (_i, [_p, _p, _i, _i64, _i64, _i64, _p, _i, _p, _ip, _p]),
-    "tsg_bn_bwd_apply_mixed": (_i, [_p, _p, _p, _i, _i64, _i64, _i64, _p, _i, _p]),
-    "tsg_gap_ws_bytes": (_sz, [_i, _i64, _i64, _i64]),
-    "tsg_gap_fwd": (_i, [_p, _p, _i, _i, _i64, _i64, _i64, _p, _sz, _p]),
-    "tsg_gap_bwd": (_i, [_p, _p, _i, _i, _i64, _i64, _i64, _p]),
-    "tsg_adaptive_avgpool_nhwc_ws_bytes": (_sz, [_i, _i64, _i, _i, _i, _i, _i]),
-    "tsg_adaptive_avgpool_nhwc_fwd": (_i, [_p, _p, _i, _i64, _i, _i, _i, _i, _i, _p, _sz, _p]),
-    "tsg_adaptive_avgpool_nhwc_bwd": (_i, [_p, _p, _i, _i64, _i, _i, _i, _i, _i, _p]),
-    "tsg_cat2_rows": (_i, [_p, _p, _p, _i64, _i64, _i64, _p]),
-    "tsg_chanscale_fwd": (_i, [_p, _p, _p, _i, _i, _i64, _i64, _i64, _i, _p]),
-    "tsg_chanscale_bwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i64, _i64, _i64, _i, _p, _sz, _p]),
-    "tsg_chanscale_bwd_ds": (_i, [_p, _p, _p, _i, _i, _i64, _i64, _i64, _p, _sz, _p]),
-    "tsg_chanscale_bwd_dx": (_i, [_p, _p, _p, _p, _i, _i, _i64, _i64, _i64, _i, _p]),
-    "tsg_maxpool_nhwc_fwd": (_i, [_p, _p, _p, _i, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
-    "tsg_maxpool_nhwc_bwd": (_i, [_p, _p, _p, _i, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
-    "tsg_stem_conv_supported": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i64, _i64]),
-    "tsg_stem_conv_ws_bytes": (_sz, []),
-    "tsg_stem_conv_fwd": (_i, [_p, _p, _p, _i64, _i64, _i64, _p, _sz, _p]),
-    "tsg_weight_shadow_entry_bytes": (_sz, []),
-    "tsg_weight_shadow_refresh": (_i, [_p, _p, _i64, _p]),
-    "tsg_stem_conv_wrw_bn": (_i, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _sz, _p]),
-    "tsg_stem_conv_stats_partials": (_i, [_i64, _i64, _i64]),
-    "tsg_conv3x3_wrw_tr_norm": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _p, _sz, _p]),
-    "tsg_conv3x3_wrw_gen_norm": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _i, _i, _i, _p, _sz, _p]),
-    "tsg_conv3x3_c64_supported": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i]),
-    "tsg_conv3x3_c64_stats_partials": (_i, [_i64, _i64, _i64]),
-    "tsg_conv3x3_c64_fwd": (_i, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p]),
-    "tsg_conv3x3_c64_s2_stats_partials": (_i, [_i64, _i64, _i64]),
-    "tsg_conv3x3_c64_s2_fwd": (_i, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p]),
-    "tsg_conv3x3_c64_s2_dgrad": (_i, [_p, _p, _p, _i64, _i64, _i64, _p]),
-    "tsg_conv3x3_c64_dgrad_bnsums_partials": (_i, [_i64, _i64, _i64]),
-    "tsg_conv3x3_c64_dgrad_bnsums": (_i, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p]),
-    "tsg_conv3x3_c64_s2_dgrad_partials": (_i, [_i64, _i64, _i64]),
-    "tsg_conv3x3_c64_s2_dgrad_bnsums": (_i, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p]),
-    "tsg_conv3x3_gen_supported": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i]),
-    "tsg_conv3x3_gen_filter_elems": (_i64, [_i, _i]),
-    "tsg_conv3x3_gen_tile": (_i, [_i64, _i64, _i64, _i, _i]),
-    "tsg_conv3x3_gen_prep_filter": (_i, [_p, _i, _p, _i, _i, _i, _i, _p]),
-    "tsg_conv3x3_gen_stats_partials": (_i, [_i64, _i64, _i64, _i, _i, _i]),
-    "tsg_conv3x3_gen_variant": (_i, [_i64, _i64, _i64, _i, _i, _i, _i]),
-    "tsg_conv3x3_s2_dgrad_supported": (_i, [_i, _i, _i]),
-    "tsg_conv3x3_s2_dgrad": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _i, _i, _p]),
-    "tsg_conv3x3_s2_dgrad_subadd": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _i, _i, _p]),
-    "tsg_conv3x3_gen_fwd": (_i, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i, _i, _i, _p]),
-    "tsg_conv3x3_dil_supported": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i]),
-    "tsg_conv3x3_dil_stats_partials": (_i, [_i64, _i64, _i64, _i, _i, _i]),
-    "tsg_conv3x3_dil_fwd": (_i, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i, _i, _i, _p]),
-    "tsg_conv3x3_dil_wrw_ws_bytes": (_sz, [_i64, _i64, _i64, _i, _i, _i]),
-    "tsg_conv3x3_dil_wrw": (_i, [_p, _p, _p, _i64, _i64, _i64, _i, _i, _i, _p, _sz, _p]),
-    "tsg_stem3_conv_supported": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i64, _i64]),
-    "tsg_stem3_conv_ws_bytes": (_sz, []),
-    "tsg_stem3_conv_fwd": (_i, [_p, _p, _p, _i64, _i64, _i64, _p, _sz, _p]),
-    "tsg_stem3_conv_wrw": (_i, [_p, _p, _p, _i64, _i64, _i64, _p, _sz, _p]),
-    "tsg_stem_conv_fwd_stats": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _p, _sz, _p]),
-    "tsg_bn_relu_pool_fwd": (_i, [_p, _p, _p, _i, _i64, _i, _i, _i, _i, _i, _p, _p]),
-    "tsg_bn_relu_pool_bwd_num_partials": (_i, [_i, _i64, _i, _i, _i]),
-    "tsg_bn_relu_pool_bwd_reduce": (_i, [_p, _p, _p, _i, _i64, _i, _i, _i, _i, _i, _p, _p, _p]),
-    "tsg_bn_relu_pool_bwd_apply": (_i, [_p, _p, _p, _p, _i, _i64, _i, _i, _i, _i, _i, _p, _p]),
-    "tsg_stem_conv_wrw": (_i, [_p, _p, _p, _i64, _i64, _i64, _p, _sz, _p]),
-    "tsg_stem_conv_stats": (_i, [_p, _p, _p, _i64, _i64, _i64, _p, _sz, _p]),
-    "tsg_stem_conv_bn_relu_pool_fwd": (_i, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _sz, _p]),
-    "tsg_stem_pool_bwd_num_partials": (_i, [_i64, _i64, _i64]),
-    "tsg_stem_conv_bn_relu_pool_bwd_reduce": (_i, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _sz, _p]),
-    "tsg_stem_conv_wrw_bn_pool": (_i, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _sz, _p]),
-    "tsg_confusion_map": (_i, [_p, _i, _p, _i, _i64, _i, _p, _p]),
-    "tsg_confusion_logits": (_i, [_p, _i, _p, _i, _i64, _i, _i64, _i, _p, _p]),
-    "tsg_sgd_multi_blockmap": (_i64, [_p, _i, _p, _i64]),
-    "tsg_sgd_multi_step_dev": (_i, [_p, _p, _p, _p, _p, _i, _p, _p, _p, _i, _p, _i64, _f, _p]),
-    "tsg_conv3x3_wrw_supported": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i]),
-    "tsg_conv3x3_wrw_ws_bytes": (_sz, []),
-    "tsg_conv3x3_wrw": (_i, [_p, _p, _p, _i64, _i64, _i64, _p, _sz, _p]),
-    "tsg_conv3x3_wrw_tr": (_i, [_p, _p, _p, _i64, _i64, _i64, _p, _sz, _p]),
-    "tsg_conv3x3_wrw_gen_supported": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i]),
-    "tsg_conv3x3_wrw_gen_ws_bytes": (_sz, [_i64, _i64, _i64, _i, _i, _i]),
-    "tsg_conv3x3_wrw_gen": (_i, [_p, _p, _p, _i64, _i64, _i64, _i, _i, _i, _p, _sz, _p]),
-    "tsg_conv3x3_weight_rot180_t": (_i, [_p, _i, _p, _i, _i, _p]),
-    "tsg_multi_copy_f32": (_i, [_p, _p, _p, _i, _p, _i64, _f, _p]),
-    "tsg_ohem_make_plan": (_i, [_i64, _i, _i64, _f, C.POINTER(OhemPlan)]),
-    "tsg_ohem_fwd": (_i, [_p, _i, _p, _i, _i64, _i, _i64, _i64, _f, _i64, _p, _p, _p, _p, _p, _p, _sz, _p]),
-    "tsg_ohem_bwd": (_i, [_p, _i, _p, _i, _i64, _i, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p]),
-    "tsg_ohem_up_supported": (_i, [_i, _i, _i, _i, _i, _f]),
-    "tsg_ohem_up_fwd": (_i, [_p, _i, _p, _i, _i64, _i, _i, _i, _i, _i, _i64, _f, _i64, _p, _p, _p, _p, _p, _p, _sz, _p]),
-    "tsg_ohem_up_bwd_ws_bytes": (_sz, [_i64, _i, _i, _i]),
-    "tsg_ohem_up_bwd": (_i, [_p, _i, _p, _i, _i64, _i, _i, _i, _i, _i, _i64, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
-    "tsg_ohem_target_prob": (_i, [_p, _p, _i, _i64, _i, _i64, _p, _p]),
-    "tsg_kth_ws_bytes": (_sz, [_i64]),
-    "tsg_kth_value": (_i, [_p, _i64, _i64, _p, _p, _sz, _p]),
-    "tsg_focal_ws_bytes": (_sz, [_i64]),
-    "tsg_focal_fwd": (_i, [_p, _i, _p, _i, _i64, _i64, _f, _f, _p, _p, _sz, _p]),
-    "tsg_focal_bwd": (_i, [_p, _i, _p, _i, _i64, _i64, _f, _f, _p, _p, _p]),
-    "tsg_upsample_bilinear_ac_fwd": (_i, [_p, _p, _p, _i, _i64, _i, _i, _i, _i, _p]),
-    "tsg_upsample_bilinear_ac_bwd": (_i, [_p, _p, _i, _i64, _i, _i, _i, _i, _p]),
-    "tsg_upsample_bilinear_ac_nhwc_fwd": (_i, [_p, _p, _p, _i, _i64, _i, _i, _i, _i, _i, _p]),
-    "tsg_upsample_bilinear_ac_nhwc_bwd": (_i, [_p, _p, _i, _i64, _i, _i, _i, _i, _i, _p]),
-    "tsg_upsample_bilinear_ac_presum_fwd": (_i, [_p, _p, _p, _i, _i64, _i, _i, _i, _i, _p]),
-    "tsg_upsample_bilinear_ac_nhwc_presum_fwd": (_i, [_p, _p, _p, _i, _i64, _i, _i, _i, _i, _i, _p]),
-    "tsg_upsample_nearest_fwd": (_i, [_p, _p, _i, _i64, _i, _i, _i, _i, _p]),
-    "tsg_psa_ws_bytes": (_sz, [_i, _i, _i64, _i64, _i64, _i64]),
-    "tsg_psa_fwd": (_i, [_p, _p, _p, _p, _i, _i64, _i64, _i64, _i64, _p, _sz, _p]),
-    "tsg_psa_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i64, _i64, _i64, _i64, _p, _sz, _p]),
-    "tsg_augment_max_samples": (_i, []),
-    "tsg_augment_crop": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _p, _f, _i, _p, _p, _i, _p]),
-    "tsg_resize_bilinear_hp": (_i, [_p, _p, _i, _i64, _i, _i, _i, _i, _i, _p]),
-    "tsg_comm_init_library": (_i, [C.c_char_p]),
-    "tsg_comm_unique_id_bytes": (_i, []),
-    "tsg_comm_get_unique_id": (_i, [_p]),
-    "tsg_comm_create": (_i, [_p, _i, _i, _i, C.POINTER(_p)]),
-    "tsg_comm_destroy": (_i, [_p]),
-    "tsg_comm_rank": (_i, [_p]),
-    "tsg_comm_world": (_i, [_p]),
-    "tsg_comm_allreduce": (_i, [_p, _p, _i64, _i, _p]),
-    "tsg_comm_allgather": (_i, [_p, _p, _p, _i64, _i, _p]),
-    "tsg_comm_reduce_scatter": (_i, [_p, _p, _p, _i64, _i, _p]),
-    "tsg_comm_broadcast": (_i, [_p, _p, _i64, _i, _i, _p]),
-    "tsg_comm_error_string": (C.c_char_p, [_i]),
-    "tsg_comm_xgmi_handle_bytes": (_sz, []),
-    "tsg_comm_xgmi_export": (_i, [_p, _i64, _p]),
-    "tsg_comm_xgmi_attach": (_i, [_p, _p]),
-    "tsg_xgmi_small_allreduce": (_i, [_p, _p, _i64, _p]),
-    "tsg_sgd_step_dev": (_i, [_p, _p, _p, _i64, _p, _f, _f, _f, _f, _p]),
-    "tsg_sgd_step": (_i, [_p, _p, _p, _i64, _f, _f, _f, _f, _i, _p]),
-    "tsg_edge_labels_ws_bytes": (_sz, [_i, _i]),
-    "tsg_edge_labels": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _i, _p, _sz, _p]),
-    "tsg_conv1x1_vec_supported": (_i, [_i, _i, _i]),
-    "tsg_conv1x1_vec_fwd": (_i, [_p, _p, _p, _i, _i, _i, _p]),
-    "tsg_conv1x1_vec_bwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p]),
-    "tsg_conv1x1_vec_bnact_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _f, _f, _i, _i, _i, _i, _i, _p]),
-    "tsg_conv1x1_vec_bnact_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
-    "tsg_cls_head_supported": (_i, [_i, _i, _i, _i64]),
-    "tsg_cls_head_fwd": (_i, [_p, _p, _p, _p, _i64, _i64, _i, _i, _p]),
-    "tsg_cls_head_dgrad": (_i, [_p, _p, _p, _i64, _i64, _i, _i, _p]),
-    "tsg_cls_head_wgrad_ws_bytes": (_sz, [_i64, _i, _i]),
-    "tsg_cls_head_wgrad": (_i, [_p, _p, _p, _p, _i64, _i64, _i, _i, _p, _sz, _p]),
-    "tsg_conv2d_f32_exact_fwd": (_i, [_p, _p, _p, _i64] + [_i] * 12 + [_p, _p, _p, _p]),
-    "tsg_conv2d_f32_exact_dgrad": (_i, [_p, _p, _p, _i64] + [_i] * 12 + [_p, _p, _p, _p]),
-    "tsg_conv2d_f32_exact_wgrad_ws_bytes": (_sz, [_i64] + [_i] * 12),
-    "tsg_conv2d_f32_exact_wgrad": (_i, [_p, _p, _p, _i64] + [_i] * 12 + [_p, _p, _p, _p, _sz, _p]),
-    "tsg_dwconv3x3_supported": (_i, [_i] * 10),
-    "tsg_dwconv3x3_fwd": (_i, [_p, _p, _p, _i, _i64, _i, _i, _i, _i, _p]),
-    "tsg_dwconv3x3_dgrad": (_i, [_p, _p, _p, _i, _i64, _i, _i, _i, _i, _p]),
-    "tsg_dwconv3x3_wgrad_ws_bytes": (_sz, [_i64, _i, _i, _i, _i, _i]),
-    "tsg_dwconv3x3_wgrad": (_i, [_p, _p, _p, _i, _i64, _i, _i, _i, _i, _p, _sz, _p]),
-    "tsg_seg_tail_logprob_supported": (_i, [_i] * 6),
-    "tsg_seg_tail_logprob": (_i, [_p, _i, _i64, _i, _i, _i, _i, _i, _p, _p]),
-    "tsg_seg_tail_accum_supported": (_i, [_i] * 8),
-    "tsg_seg_tail_accum": (_i, [_p, _p, _i, _i64, _i, _i, _i, _i, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
-}
+# The closed type map of the C-ABI.  By value: exactly these spellings.  Pointers, ONE rule: every pointer parameter is
+# c_void_p (it takes None, an integer address, byref(...) and ctypes pointers alike), except `const char*`, which is
+# c_char_p as a parameter and as a return type.  Anything else is an error, never a default.
+_VALUES = {"int": C.c_int, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t}
+_DECL = re.compile(r"(.+?)\b(tsg_\w+)\s*\(([^()]*)\)", re.S)
+
+
+def _ctype(spelling, decl, named):
+    """ctypes type of a return type (named = False) or of a parameter, whose last word is its name"""
+    t = " ".join(spelling.replace("*", " * ").split())
+    if "*" in t:
+        if named:
+            t = t.rsplit("*", 1)[0] + "*"
+        return C.c_char_p if t == "const char *" else C.c_void_p
+    if named and " " in t:
+        t = t.rsplit(" ", 1)[0]
+    if t not in _VALUES:
+        raise TsgError(f"C-ABI header: no ctypes mapping for '{spelling.strip()}' in `{' '.join(decl.split())}`")
+    return _VALUES[t]
+
+
+def _parse_protos(text):
+    """name -> (restype, argtypes) of every `RET tsg_name(ARGS);` declaration of a C header"""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M).replace('extern "C" {', "")
+    protos = {}
+    for decl in text.split(";"):
+        if "(" not in decl:
+            continue            # enums, the fields of a struct, typedefs
+        m = _DECL.fullmatch(decl.strip())
+        if m is None:
+            raise TsgError(f"C-ABI header: cannot read `{' '.join(decl.split())}`")
+        ret, name, args = m.groups()
+        args = [] if args.strip() in ("", "void") else args.split(",")
+        protos[name] = (_ctype(ret, decl, False), [_ctype(a, decl, True) for a in args])
+    return protos
+
+
+with open(_HEADER) as _f:
+    _PROTOS = _parse_protos(_f.read())
 
 _lib = None
 
@@ -237,6 +112,13 @@ def check(rc, what):
     if rc < 0:
         raise TsgError(f"{what}: invalid argument ({_ERR.get(rc, rc)})")
     raise TsgError(f"{what}: hipError_t {rc}")
+
+
+def call(fn, *args):
+    """fn(*args) for an entry point whose int result is a status: non-zero raises, named after the entry point called"""
+    rc = fn(*args)
+    if rc:
+        check(rc, fn.__name__)
 
 
 def ptr(t):

@@ -61,7 +61,7 @@ class Comm(object):
                 n = self.lib.tsg_comm_unique_id_bytes()
                 buf = C.create_string_buffer(n)
                 if self.rank == 0:
-                    L.check(self.lib.tsg_comm_get_unique_id(buf), "tsg_comm_get_unique_id")
+                    L.call(self.lib.tsg_comm_get_unique_id, buf)
                     ident = buf.raw
         except Exception as e:                                 # noqa: BLE001 - the other ranks must hear of it, whatever it was
             err = e
@@ -76,7 +76,7 @@ class Comm(object):
         try:                                                   # 4
             handle = C.c_void_p()
             idbuf = C.create_string_buffer(ident, len(ident)) if rccl else None
-            L.check(self.lib.tsg_comm_create(idbuf, self.rank, self.world, self.device, C.byref(handle)), "tsg_comm_create")
+            L.call(self.lib.tsg_comm_create, idbuf, self.rank, self.world, self.device, C.byref(handle))
             self.handle = handle
         except Exception as e:                                 # noqa: BLE001
             err = e
@@ -101,7 +101,7 @@ class Comm(object):
         try:
             hb = self.lib.tsg_comm_xgmi_handle_bytes()
             buf = C.create_string_buffer(hb)
-            L.check(self.lib.tsg_comm_xgmi_export(self.handle, _MAX_SMALL, buf), "tsg_comm_xgmi_export")
+            L.call(self.lib.tsg_comm_xgmi_export, self.handle, _MAX_SMALL, buf)
             mine = buf.raw
         except Exception as e:                                 # noqa: BLE001
             import warnings
@@ -112,7 +112,7 @@ class Comm(object):
         if ok:
             try:
                 allh = C.create_string_buffer(b"".join(handles), hb * self.world)
-                L.check(self.lib.tsg_comm_xgmi_attach(self.handle, allh), "tsg_comm_xgmi_attach")
+                L.call(self.lib.tsg_comm_xgmi_attach, self.handle, allh)
             except Exception as e:                             # noqa: BLE001
                 import warnings
                 warnings.warn("torchseg_amd.comm: mailbox attach failed (%s); SyncBN messages stay on RCCL" % (e,))
@@ -129,8 +129,7 @@ class Comm(object):
     def all_reduce(self, t):
         """t <- sum over ranks, in place, on the current stream."""
         self._check(t)
-        L.check(self.lib.tsg_comm_allreduce(self.handle, t.data_ptr(), t.numel(), L.dtype_code(t), L.stream_ptr(t)),
-                "tsg_comm_allreduce")
+        L.call(self.lib.tsg_comm_allreduce, self.handle, t.data_ptr(), t.numel(), L.dtype_code(t), L.stream_ptr(t))
         return t
 
     def small_all_reduce(self, t):
@@ -138,8 +137,7 @@ class Comm(object):
         self._check(t)
         if t.dtype != torch.float32:
             raise L.TsgError("small_all_reduce takes float32 messages")
-        L.check(self.lib.tsg_xgmi_small_allreduce(self.handle, t.data_ptr(), t.numel(), L.stream_ptr(t)),
-                "tsg_xgmi_small_allreduce")
+        L.call(self.lib.tsg_xgmi_small_allreduce, self.handle, t.data_ptr(), t.numel(), L.stream_ptr(t))
         return t
 
     def all_gather(self, send, recv):
@@ -147,8 +145,8 @@ class Comm(object):
         self._check(recv)
         if recv.numel() != send.numel() * self.world or recv.dtype != send.dtype:
             raise L.TsgError("all_gather: recv must hold world x send")
-        L.check(self.lib.tsg_comm_allgather(self.handle, send.data_ptr(), recv.data_ptr(), send.numel(),
-                                            L.dtype_code(send), L.stream_ptr(send)), "tsg_comm_allgather")
+        L.call(self.lib.tsg_comm_allgather, self.handle, send.data_ptr(), recv.data_ptr(), send.numel(), L.dtype_code(send),
+               L.stream_ptr(send))
         return recv
 
     def reduce_scatter(self, send, recv):
@@ -157,14 +155,13 @@ class Comm(object):
         self._check(recv)
         if send.numel() != recv.numel() * self.world or recv.dtype != send.dtype:
             raise L.TsgError("reduce_scatter: send must hold world x recv")
-        L.check(self.lib.tsg_comm_reduce_scatter(self.handle, send.data_ptr(), recv.data_ptr(), recv.numel(),
-                                                 L.dtype_code(send), L.stream_ptr(send)), "tsg_comm_reduce_scatter")
+        L.call(self.lib.tsg_comm_reduce_scatter, self.handle, send.data_ptr(), recv.data_ptr(), recv.numel(),
+               L.dtype_code(send), L.stream_ptr(send))
         return recv
 
     def broadcast(self, t, root=0):
         self._check(t)
-        L.check(self.lib.tsg_comm_broadcast(self.handle, t.data_ptr(), t.numel(), L.dtype_code(t), int(root),
-                                            L.stream_ptr(t)), "tsg_comm_broadcast")
+        L.call(self.lib.tsg_comm_broadcast, self.handle, t.data_ptr(), t.numel(), L.dtype_code(t), int(root), L.stream_ptr(t))
         return t
 
     def destroy(self):

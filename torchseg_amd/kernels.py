@@ -69,42 +69,35 @@ class HipKernels:
         self.lib = L.lib()
         self._npart = {}
 
-    def _count(self, key, fn, what):
-        """A (cached) geometry query of the library whose non-negative result is a count."""
+    def _count(self, fn, *args, may_be_zero=False):
+        """fn(*args), cached: a geometry query of the library whose positive result is a count.  0 is an answer only for a
+        query that doubles as a yes/no (may_be_zero, which also hands an error code back as a 'no'); otherwise anything
+        below 1 raises."""
+        key = (fn.__name__,) + args
         v = self._npart.get(key)
         if v is None:
-            v = fn()
-            if v <= 0:
-                L.check(v if v < 0 else -2, what)
-            self._npart[key] = v
-        return v
-
-    def _num_partials(self, layout, N, Cc, HW):
-        key = (layout, N, Cc, HW)
-        v = self._npart.get(key)
-        if v is None:
-            v = self._npart[key] = self.lib.tsg_bn_num_partials(layout, N, Cc, HW)
+            v = self._npart[key] = fn(*args)
+        if v <= 0 and not may_be_zero:
+            L.check(v if v < 0 else -2, fn.__name__)
         return v
 
     # ---- SyncBN -----------------------------------------------------------
     def bn_stats(self, x, layout, N, Cc, HW):
         """-> (partial fp32 [S,2,C], S)"""
         lib = self.lib
-        smax = self._num_partials(layout, N, Cc, HW)
+        smax = self._count(self.lib.tsg_bn_num_partials, layout, N, Cc, HW)
         partial = torch.empty((smax, 2, Cc), dtype=torch.float32, device=x.device)
         rows = C.c_int(0)
-        L.check(lib.tsg_bn_stats(x.data_ptr(), L.dtype_code(x), layout, N, Cc, HW,
-                                 partial.data_ptr(), C.byref(rows), L.stream_ptr(x)), "tsg_bn_stats")
+        L.call(lib.tsg_bn_stats, x.data_ptr(), L.dtype_code(x), layout, N, Cc, HW, partial.data_ptr(), C.byref(rows),
+               L.stream_ptr(x))
         return partial, rows.value
 
     def bn_collapse(self, partial, S, Cc, out, count=None):
         """out[0:2C] = per-channel sums; with `count` also out[2C:2C+2] = the element count as two exact fp32 words"""
         if count is None:
-            L.check(self.lib.tsg_bn_collapse(partial.data_ptr(), S, Cc, out.data_ptr(),
-                                             L.stream_ptr(partial)), "tsg_bn_collapse")
+            L.call(self.lib.tsg_bn_collapse, partial.data_ptr(), S, Cc, out.data_ptr(), L.stream_ptr(partial))
         else:
-            L.check(self.lib.tsg_bn_collapse_count(partial.data_ptr(), S, Cc, out.data_ptr(), int(count),
-                                                   L.stream_ptr(partial)), "tsg_bn_collapse_count")
+            L.call(self.lib.tsg_bn_collapse_count, partial.data_ptr(), S, Cc, out.data_ptr(), int(count), L.stream_ptr(partial))
 
     def bn_finalize(self, partial, S, Cc, count, count_dev, eps, momentum, gamma, beta,
                     running_mean, running_var, nbt):
@@ -113,36 +106,32 @@ class HipKernels:
         mean = torch.empty(Cc, dtype=torch.float32, device=dev)
         invstd = torch.empty(Cc, dtype=torch.float32, device=dev)
         fp = torch.empty((3, Cc), dtype=torch.float32, device=dev)
-        L.check(self.lib.tsg_bn_finalize(partial.data_ptr(), S, Cc, float(count), L.ptr(count_dev),
-                                         eps, momentum, L.ptr(gamma), L.ptr(beta), L.ptr(running_mean),
-                                         L.ptr(running_var), L.ptr(nbt), mean.data_ptr(),
-                                         invstd.data_ptr(), fp.data_ptr(), L.stream_ptr(partial)),
-                "tsg_bn_finalize")
+        L.call(self.lib.tsg_bn_finalize, partial.data_ptr(), S, Cc, float(count), L.ptr(count_dev), eps, momentum, L.ptr(gamma),
+               L.ptr(beta), L.ptr(running_mean), L.ptr(running_var), L.ptr(nbt), mean.data_ptr(), invstd.data_ptr(),
+               fp.data_ptr(), L.stream_ptr(partial))
         return mean, invstd, fp
 
     def bn_affine(self, mean, invstd, gamma, beta):
         Cc = mean.numel()
         fp = torch.empty((3, Cc), dtype=torch.float32, device=mean.device)
-        L.check(self.lib.tsg_bn_affine(mean.data_ptr(), invstd.data_ptr(), L.ptr(gamma), L.ptr(beta), Cc,
-                                       fp.data_ptr(), L.stream_ptr(mean)), "tsg_bn_affine")
+        L.call(self.lib.tsg_bn_affine, mean.data_ptr(), invstd.data_ptr(), L.ptr(gamma), L.ptr(beta), Cc, fp.data_ptr(),
+               L.stream_ptr(mean))
         return fp
 
     def bn_apply_fwd(self, x, residual, layout, N, Cc, HW, fp, relu, out=None):
         y = torch.empty_like(x) if out is None else out
-        L.check(self.lib.tsg_bn_apply_fwd(x.data_ptr(), L.ptr(residual), y.data_ptr(),
-                                          L.dtype_code(x), layout, N, Cc, HW, fp.data_ptr(),
-                                          int(relu), L.stream_ptr(x)), "tsg_bn_apply_fwd")
+        L.call(self.lib.tsg_bn_apply_fwd, x.data_ptr(), L.ptr(residual), y.data_ptr(), L.dtype_code(x), layout, N, Cc, HW,
+               fp.data_ptr(), int(relu), L.stream_ptr(x))
         return y
 
     def bn_bwd_reduce(self, dy, x, y, layout, N, Cc, HW, fp, relu):
         """-> (partial fp32 [S,2,C] = {sum dy', sum dy'(x-mean)}, S)"""
         lib = self.lib
-        smax = self._num_partials(layout, N, Cc, HW)
+        smax = self._count(self.lib.tsg_bn_num_partials, layout, N, Cc, HW)
         partial = torch.empty((smax, 2, Cc), dtype=torch.float32, device=x.device)
         rows = C.c_int(0)
-        L.check(lib.tsg_bn_bwd_reduce(dy.data_ptr(), x.data_ptr(), L.ptr(y), L.dtype_code(x),
-                                      layout, N, Cc, HW, fp.data_ptr(), int(relu), partial.data_ptr(),
-                                      C.byref(rows), L.stream_ptr(x)), "tsg_bn_bwd_reduce")
+        L.call(lib.tsg_bn_bwd_reduce, dy.data_ptr(), x.data_ptr(), L.ptr(y), L.dtype_code(x), layout, N, Cc, HW, fp.data_ptr(),
+               int(relu), partial.data_ptr(), C.byref(rows), L.stream_ptr(x))
         return partial, rows.value
 
     def bn_bwd_coeffs(self, partial, S, Cc, count, count_dev, batch_stats, invstd, fp,
@@ -152,18 +141,15 @@ class HipKernels:
         dgamma = torch.empty(Cc, dtype=torch.float32, device=dev) if want_param_grads else None
         dbeta = torch.empty(Cc, dtype=torch.float32, device=dev) if want_param_grads else None
         bp = torch.empty((5, Cc), dtype=torch.float32, device=dev) if want_pack else None
-        L.check(self.lib.tsg_bn_bwd_coeffs(partial.data_ptr(), S, Cc, float(count), L.ptr(count_dev),
-                                           int(batch_stats), invstd.data_ptr(), L.ptr(fp), L.ptr(dgamma),
-                                           L.ptr(dbeta), L.ptr(bp), L.stream_ptr(partial)),
-                "tsg_bn_bwd_coeffs")
+        L.call(self.lib.tsg_bn_bwd_coeffs, partial.data_ptr(), S, Cc, float(count), L.ptr(count_dev), int(batch_stats),
+               invstd.data_ptr(), L.ptr(fp), L.ptr(dgamma), L.ptr(dbeta), L.ptr(bp), L.stream_ptr(partial))
         return dgamma, dbeta, bp
 
     def bn_bwd_apply(self, dy, x, y, layout, N, Cc, HW, bp, relu, want_dres):
         dx = torch.empty_like(x)
         dres = torch.empty_like(x) if want_dres else None
-        L.check(self.lib.tsg_bn_bwd_apply(dy.data_ptr(), x.data_ptr(), L.ptr(y), dx.data_ptr(),
-                                          L.ptr(dres), L.dtype_code(x), layout, N, Cc, HW,
-                                          bp.data_ptr(), int(relu), L.stream_ptr(x)), "tsg_bn_bwd_apply")
+        L.call(self.lib.tsg_bn_bwd_apply, dy.data_ptr(), x.data_ptr(), L.ptr(y), dx.data_ptr(), L.ptr(dres), L.dtype_code(x),
+               layout, N, Cc, HW, bp.data_ptr(), int(relu), L.stream_ptr(x))
         return dx, dres
 
     # ---- SyncBN block tail with the ReLU mask as one bit per element ------------
@@ -175,26 +161,23 @@ class HipKernels:
         y = torch.empty_like(x)
         V = 8 if x.dtype == torch.bfloat16 else 4
         bits = torch.empty(N * HW * Cc // V, dtype=torch.uint8, device=x.device)
-        L.check(self.lib.tsg_bn_apply_fwd_maskbits(x.data_ptr(), L.ptr(residual), y.data_ptr(), bits.data_ptr(),
-                                                   L.dtype_code(x), layout, N, Cc, HW, fp.data_ptr(), L.stream_ptr(x)),
-                "tsg_bn_apply_fwd_maskbits")
+        L.call(self.lib.tsg_bn_apply_fwd_maskbits, x.data_ptr(), L.ptr(residual), y.data_ptr(), bits.data_ptr(),
+               L.dtype_code(x), layout, N, Cc, HW, fp.data_ptr(), L.stream_ptr(x))
         return y, bits
 
     def bn_bwd_reduce_bits(self, dy, x, bits, layout, N, Cc, HW, fp):
-        smax = self._num_partials(layout, N, Cc, HW)
+        smax = self._count(self.lib.tsg_bn_num_partials, layout, N, Cc, HW)
         partial = torch.empty((smax, 2, Cc), dtype=torch.float32, device=x.device)
         rows = C.c_int(0)
-        L.check(self.lib.tsg_bn_bwd_reduce_maskbits(dy.data_ptr(), x.data_ptr(), bits.data_ptr(), L.dtype_code(x), layout, N,
-                                                    Cc, HW, fp.data_ptr(), partial.data_ptr(), C.byref(rows),
-                                                    L.stream_ptr(x)), "tsg_bn_bwd_reduce_maskbits")
+        L.call(self.lib.tsg_bn_bwd_reduce_maskbits, dy.data_ptr(), x.data_ptr(), bits.data_ptr(), L.dtype_code(x), layout, N,
+               Cc, HW, fp.data_ptr(), partial.data_ptr(), C.byref(rows), L.stream_ptr(x))
         return partial, rows.value
 
     def bn_bwd_apply_bits(self, dy, x, bits, layout, N, Cc, HW, bp, want_dres):
         dx = torch.empty_like(x)
         dres = torch.empty_like(x) if want_dres else None
-        L.check(self.lib.tsg_bn_bwd_apply_maskbits(dy.data_ptr(), x.data_ptr(), bits.data_ptr(), dx.data_ptr(), L.ptr(dres),
-                                                   L.dtype_code(x), layout, N, Cc, HW, bp.data_ptr(), L.stream_ptr(x)),
-                "tsg_bn_bwd_apply_maskbits")
+        L.call(self.lib.tsg_bn_bwd_apply_maskbits, dy.data_ptr(), x.data_ptr(), bits.data_ptr(), dx.data_ptr(), L.ptr(dres),
+               L.dtype_code(x), layout, N, Cc, HW, bp.data_ptr(), L.stream_ptr(x))
         return dx, dres
 
     # ---- SyncBN, mixed layout (x NCHW, y/dy channels_last) -------------------
@@ -206,25 +189,22 @@ class HipKernels:
 
     def bn_apply_fwd_mixed(self, x, N, Cc, HW, fp, relu):
         y = torch.empty_like(x, memory_format=torch.channels_last)
-        L.check(self.lib.tsg_bn_apply_fwd_mixed(x.data_ptr(), y.data_ptr(), L.dtype_code(x), N, Cc, HW,
-                                                fp.data_ptr(), int(relu), L.stream_ptr(x)),
-                "tsg_bn_apply_fwd_mixed")
+        L.call(self.lib.tsg_bn_apply_fwd_mixed, x.data_ptr(), y.data_ptr(), L.dtype_code(x), N, Cc, HW, fp.data_ptr(),
+               int(relu), L.stream_ptr(x))
         return y
 
     def bn_bwd_reduce_mixed(self, dy, x, N, Cc, HW, fp, relu):
         smax = self.lib.tsg_bn_mixed_num_partials(N, Cc, HW)
         partial = torch.empty((smax, 2, Cc), dtype=torch.float32, device=x.device)
         rows = C.c_int(0)
-        L.check(self.lib.tsg_bn_bwd_reduce_mixed(dy.data_ptr(), x.data_ptr(), L.dtype_code(x), N, Cc, HW,
-                                                 fp.data_ptr(), int(relu), partial.data_ptr(),
-                                                 C.byref(rows), L.stream_ptr(x)), "tsg_bn_bwd_reduce_mixed")
+        L.call(self.lib.tsg_bn_bwd_reduce_mixed, dy.data_ptr(), x.data_ptr(), L.dtype_code(x), N, Cc, HW, fp.data_ptr(),
+               int(relu), partial.data_ptr(), C.byref(rows), L.stream_ptr(x))
         return partial, rows.value
 
     def bn_bwd_apply_mixed(self, dy, x, N, Cc, HW, bp, relu):
         dx = torch.empty_like(x)
-        L.check(self.lib.tsg_bn_bwd_apply_mixed(dy.data_ptr(), x.data_ptr(), dx.data_ptr(), L.dtype_code(x),
-                                                N, Cc, HW, bp.data_ptr(), int(relu), L.stream_ptr(x)),
-                "tsg_bn_bwd_apply_mixed")
+        L.call(self.lib.tsg_bn_bwd_apply_mixed, dy.data_ptr(), x.data_ptr(), dx.data_ptr(), L.dtype_code(x), N, Cc, HW,
+               bp.data_ptr(), int(relu), L.stream_ptr(x))
         return dx
 
     # ---- global average pool -------------------------------------------------
@@ -232,14 +212,13 @@ class HipKernels:
         wsb = self.lib.tsg_gap_ws_bytes(layout, N, Cc, HW)
         ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=x.device)
         out = torch.empty((N, Cc), dtype=x.dtype, device=x.device)
-        L.check(self.lib.tsg_gap_fwd(x.data_ptr(), out.data_ptr(), L.dtype_code(x), layout, N, Cc, HW,
-                                     ws.data_ptr(), ws.numel(), L.stream_ptr(x)), "tsg_gap_fwd")
+        L.call(self.lib.tsg_gap_fwd, x.data_ptr(), out.data_ptr(), L.dtype_code(x), layout, N, Cc, HW, ws.data_ptr(),
+               ws.numel(), L.stream_ptr(x))
         return out
 
     def gap_bwd(self, dout, like, layout, N, Cc, HW):
         dx = torch.empty_like(like)
-        L.check(self.lib.tsg_gap_bwd(dout.data_ptr(), dx.data_ptr(), L.dtype_code(dout), layout, N, Cc, HW,
-                                     L.stream_ptr(dout)), "tsg_gap_bwd")
+        L.call(self.lib.tsg_gap_bwd, dout.data_ptr(), dx.data_ptr(), L.dtype_code(dout), layout, N, Cc, HW, L.stream_ptr(dout))
         return dx
 
     def adaptive_avgpool_supported(self, x, OH, OW):
@@ -255,17 +234,16 @@ class HipKernels:
         wsb = self.lib.tsg_adaptive_avgpool_nhwc_ws_bytes(L.dtype_code(x), N, Cc, H, W, OH, OW)
         ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=x.device)
         out = torch.empty((N, Cc, OH, OW), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-        L.check(self.lib.tsg_adaptive_avgpool_nhwc_fwd(x.data_ptr(), out.data_ptr(), L.dtype_code(x), N, Cc, H, W, OH, OW,
-                                                       ws.data_ptr(), ws.numel(), L.stream_ptr(x)),
-                "tsg_adaptive_avgpool_nhwc_fwd")
+        L.call(self.lib.tsg_adaptive_avgpool_nhwc_fwd, x.data_ptr(), out.data_ptr(), L.dtype_code(x), N, Cc, H, W, OH, OW,
+               ws.data_ptr(), ws.numel(), L.stream_ptr(x))
         return out
 
     def adaptive_avgpool_bwd(self, dout, H, W):
         """dout [N,C,OH,OW] channels_last -> dx [N,C,H,W] channels_last"""
         N, Cc, OH, OW = dout.shape
         dx = torch.empty((N, Cc, H, W), dtype=dout.dtype, device=dout.device, memory_format=torch.channels_last)
-        L.check(self.lib.tsg_adaptive_avgpool_nhwc_bwd(dout.data_ptr(), dx.data_ptr(), L.dtype_code(dout), N, Cc, H, W, OH,
-                                                       OW, L.stream_ptr(dout)), "tsg_adaptive_avgpool_nhwc_bwd")
+        L.call(self.lib.tsg_adaptive_avgpool_nhwc_bwd, dout.data_ptr(), dx.data_ptr(), L.dtype_code(dout), N, Cc, H, W, OH, OW,
+               L.stream_ptr(dout))
         return dx
 
     def cat_channels(self, a, b):
@@ -274,14 +252,13 @@ class HipKernels:
         Cb = b.shape[1]
         out = torch.empty((B, Ca + Cb, H, W), dtype=a.dtype, device=a.device, memory_format=torch.channels_last)
         es = a.element_size()
-        L.check(self.lib.tsg_cat2_rows(a.data_ptr(), b.data_ptr(), out.data_ptr(), B * H * W, Ca * es, Cb * es, L.stream_ptr(a)),
-                "tsg_cat2_rows")
+        L.call(self.lib.tsg_cat2_rows, a.data_ptr(), b.data_ptr(), out.data_ptr(), B * H * W, Ca * es, Cb * es, L.stream_ptr(a))
         return out
 
     def chanscale_fwd(self, x, s, layout, N, Cc, HW, add_identity):
         y = torch.empty_like(x)
-        L.check(self.lib.tsg_chanscale_fwd(x.data_ptr(), s.data_ptr(), y.data_ptr(), L.dtype_code(x), layout,
-                                           N, Cc, HW, int(add_identity), L.stream_ptr(x)), "tsg_chanscale_fwd")
+        L.call(self.lib.tsg_chanscale_fwd, x.data_ptr(), s.data_ptr(), y.data_ptr(), L.dtype_code(x), layout, N, Cc, HW,
+               int(add_identity), L.stream_ptr(x))
         return y
 
     def chanscale_bwd(self, dy, x, s, layout, N, Cc, HW, add_identity):
@@ -289,9 +266,8 @@ class HipKernels:
         ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=x.device)
         dx = torch.empty_like(x)
         ds = torch.empty((N, Cc), dtype=x.dtype, device=x.device)
-        L.check(self.lib.tsg_chanscale_bwd(dy.data_ptr(), x.data_ptr(), s.data_ptr(), dx.data_ptr(), ds.data_ptr(),
-                                           L.dtype_code(x), layout, N, Cc, HW, int(add_identity), ws.data_ptr(),
-                                           ws.numel(), L.stream_ptr(x)), "tsg_chanscale_bwd")
+        L.call(self.lib.tsg_chanscale_bwd, dy.data_ptr(), x.data_ptr(), s.data_ptr(), dx.data_ptr(), ds.data_ptr(),
+               L.dtype_code(x), layout, N, Cc, HW, int(add_identity), ws.data_ptr(), ws.numel(), L.stream_ptr(x))
         return dx, ds
 
     def chanscale_split_supported(self, x, layout, Cc):
@@ -303,15 +279,15 @@ class HipKernels:
         wsb = self.lib.tsg_gap_ws_bytes(layout, N, Cc, HW)
         ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=x.device)
         ds = torch.empty((N, Cc), dtype=x.dtype, device=x.device)
-        L.check(self.lib.tsg_chanscale_bwd_ds(dy.data_ptr(), x.data_ptr(), ds.data_ptr(), L.dtype_code(x), layout, N, Cc, HW,
-                                              ws.data_ptr(), ws.numel(), L.stream_ptr(x)), "tsg_chanscale_bwd_ds")
+        L.call(self.lib.tsg_chanscale_bwd_ds, dy.data_ptr(), x.data_ptr(), ds.data_ptr(), L.dtype_code(x), layout, N, Cc, HW,
+               ws.data_ptr(), ws.numel(), L.stream_ptr(x))
         return ds
 
     def chanscale_bwd_dx(self, dy, s, gadd, layout, N, Cc, HW, add_identity):
         """dx = dy s (+ dy) + gadd[n, c] (gadd: [N, C] of dy's dtype)"""
         dx = torch.empty_like(dy)
-        L.check(self.lib.tsg_chanscale_bwd_dx(dy.data_ptr(), s.data_ptr(), gadd.data_ptr(), dx.data_ptr(), L.dtype_code(dy), layout,
-                                              N, Cc, HW, int(add_identity), L.stream_ptr(dy)), "tsg_chanscale_bwd_dx")
+        L.call(self.lib.tsg_chanscale_bwd_dx, dy.data_ptr(), s.data_ptr(), gadd.data_ptr(), dx.data_ptr(), L.dtype_code(dy),
+               layout, N, Cc, HW, int(add_identity), L.stream_ptr(dy))
         return dx
 
     # ---- max pool (channels_last) ------------------------------------------------
@@ -321,16 +297,16 @@ class HipKernels:
         OH, OW = (IH + 2 * P_ - K_) // S_ + 1, (IW + 2 * P_ - K_) // S_ + 1
         y = torch.empty((N, Cc, OH, OW), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
         idx = torch.empty((N, OH, OW, Cc), dtype=torch.uint8, device=x.device)
-        L.check(self.lib.tsg_maxpool_nhwc_fwd(x.data_ptr(), y.data_ptr(), idx.data_ptr(), L.dtype_code(x), N, Cc,
-                                              IH, IW, OH, OW, K_, S_, P_, L.stream_ptr(x)), "tsg_maxpool_nhwc_fwd")
+        L.call(self.lib.tsg_maxpool_nhwc_fwd, x.data_ptr(), y.data_ptr(), idx.data_ptr(), L.dtype_code(x), N, Cc, IH, IW, OH,
+               OW, K_, S_, P_, L.stream_ptr(x))
         return y, idx
 
     def maxpool_bwd(self, dy, idx, in_shape, K_, S_, P_):
         N, Cc, IH, IW = in_shape
         OH, OW = dy.shape[2], dy.shape[3]
         dx = torch.empty(in_shape, dtype=dy.dtype, device=dy.device, memory_format=torch.channels_last)
-        L.check(self.lib.tsg_maxpool_nhwc_bwd(dy.data_ptr(), idx.data_ptr(), dx.data_ptr(), L.dtype_code(dy), N, Cc,
-                                              IH, IW, OH, OW, K_, S_, P_, L.stream_ptr(dy)), "tsg_maxpool_nhwc_bwd")
+        L.call(self.lib.tsg_maxpool_nhwc_bwd, dy.data_ptr(), idx.data_ptr(), dx.data_ptr(), L.dtype_code(dy), N, Cc, IH, IW, OH,
+               OW, K_, S_, P_, L.stream_ptr(dy))
         return dx
 
     # ---- BN + ReLU + MaxPool2d(3, 2, 1) of the ResNet stem, fused ------------------
@@ -340,8 +316,8 @@ class HipKernels:
         OH, OW = (IH - 1) // 2 + 1, (IW - 1) // 2 + 1
         y = torch.empty((N, Cc, OH, OW), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
         idx = torch.empty((N, OH, OW, Cc), dtype=torch.uint8, device=x.device)
-        L.check(self.lib.tsg_bn_relu_pool_fwd(x.data_ptr(), y.data_ptr(), idx.data_ptr(), L.dtype_code(x), N, Cc, IH, IW,
-                                              OH, OW, fp.data_ptr(), L.stream_ptr(x)), "tsg_bn_relu_pool_fwd")
+        L.call(self.lib.tsg_bn_relu_pool_fwd, x.data_ptr(), y.data_ptr(), idx.data_ptr(), L.dtype_code(x), N, Cc, IH, IW, OH,
+               OW, fp.data_ptr(), L.stream_ptr(x))
         return y, idx
 
     def bn_relu_pool_bwd_reduce(self, dpool, idx, x, fp):
@@ -349,22 +325,18 @@ class HipKernels:
         N, Cc, IH, IW = x.shape
         OH, OW = dpool.shape[2], dpool.shape[3]
         dt = L.dtype_code(x)
-        S = self._count(("bn_pool", dt, N, Cc, IH, IW),
-                        lambda: self.lib.tsg_bn_relu_pool_bwd_num_partials(dt, N, Cc, IH, IW),
-                        "tsg_bn_relu_pool_bwd_num_partials")
+        S = self._count(self.lib.tsg_bn_relu_pool_bwd_num_partials, dt, N, Cc, IH, IW)
         partial = torch.empty((S, 2, Cc), dtype=torch.float32, device=x.device)
-        L.check(self.lib.tsg_bn_relu_pool_bwd_reduce(dpool.data_ptr(), idx.data_ptr(), x.data_ptr(), L.dtype_code(x), N, Cc,
-                                                     IH, IW, OH, OW, fp.data_ptr(), partial.data_ptr(), L.stream_ptr(x)),
-                "tsg_bn_relu_pool_bwd_reduce")
+        L.call(self.lib.tsg_bn_relu_pool_bwd_reduce, dpool.data_ptr(), idx.data_ptr(), x.data_ptr(), L.dtype_code(x), N, Cc, IH,
+               IW, OH, OW, fp.data_ptr(), partial.data_ptr(), L.stream_ptr(x))
         return partial, S
 
     def bn_relu_pool_bwd_apply(self, dpool, idx, x, bp):
         N, Cc, IH, IW = x.shape
         OH, OW = dpool.shape[2], dpool.shape[3]
         dx = torch.empty_like(x)
-        L.check(self.lib.tsg_bn_relu_pool_bwd_apply(dpool.data_ptr(), idx.data_ptr(), x.data_ptr(), dx.data_ptr(),
-                                                    L.dtype_code(x), N, Cc, IH, IW, OH, OW, bp.data_ptr(), L.stream_ptr(x)),
-                "tsg_bn_relu_pool_bwd_apply")
+        L.call(self.lib.tsg_bn_relu_pool_bwd_apply, dpool.data_ptr(), idx.data_ptr(), x.data_ptr(), dx.data_ptr(),
+               L.dtype_code(x), N, Cc, IH, IW, OH, OW, bp.data_ptr(), L.stream_ptr(x))
         return dx
 
     # ---- stem convolution ----------------------------------------------------
@@ -417,8 +389,8 @@ class HipKernels:
         y = torch.empty((B, 64, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=x.dtype, device=x.device,
                         memory_format=torch.channels_last)
         ws = self._stem_ws(x.device)
-        L.check(self.lib.tsg_stem_conv_fwd(x.data_ptr(), weight.data_ptr(), y.data_ptr(), B, H, W, ws.data_ptr(),
-                                           ws.numel(), L.stream_ptr(x)), "tsg_stem_conv_fwd")
+        L.call(self.lib.tsg_stem_conv_fwd, x.data_ptr(), weight.data_ptr(), y.data_ptr(), B, H, W, ws.data_ptr(), ws.numel(),
+               L.stream_ptr(x))
         return y
 
     def stem_conv_fwd_stats(self, x, weight):
@@ -427,12 +399,11 @@ class HipKernels:
         B, _, H, W = x.shape
         y = torch.empty((B, 64, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=x.dtype, device=x.device,
                         memory_format=torch.channels_last)
-        S = self._count(("stem_stats", B, H, W), lambda: self.lib.tsg_stem_conv_stats_partials(B, H, W),
-                        "tsg_stem_conv_stats_partials")
+        S = self._count(self.lib.tsg_stem_conv_stats_partials, B, H, W)
         partial = torch.empty((S, 2, 64), dtype=torch.float32, device=x.device)
         ws = self._stem_ws(x.device)
-        L.check(self.lib.tsg_stem_conv_fwd_stats(x.data_ptr(), weight.data_ptr(), y.data_ptr(), partial.data_ptr(), B, H,
-                                                 W, ws.data_ptr(), ws.numel(), L.stream_ptr(x)), "tsg_stem_conv_fwd_stats")
+        L.call(self.lib.tsg_stem_conv_fwd_stats, x.data_ptr(), weight.data_ptr(), y.data_ptr(), partial.data_ptr(), B, H, W,
+               ws.data_ptr(), ws.numel(), L.stream_ptr(x))
         return y, partial
 
     def stem_conv_wrw(self, x, dy):
@@ -443,8 +414,8 @@ class HipKernels:
         B, _, H, W = x.shape
         dw = torch.empty((64, 3, 7, 7), dtype=torch.float32, device=x.device)
         ws = self._stem_ws(x.device)
-        L.check(self.lib.tsg_stem_conv_wrw(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, H, W, ws.data_ptr(),
-                                           ws.numel(), L.stream_ptr(x)), "tsg_stem_conv_wrw")
+        L.call(self.lib.tsg_stem_conv_wrw, x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, H, W, ws.data_ptr(), ws.numel(),
+               L.stream_ptr(x))
         return dw
 
     # ---- deep-stem image convolution (3x3 / s2 / p1, 3 -> 64) ------------------
@@ -462,8 +433,8 @@ class HipKernels:
         y = torch.empty((B, 64, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=x.dtype, device=x.device,
                         memory_format=torch.channels_last)
         ws = self._scratch("stem3", self.lib.tsg_stem3_conv_ws_bytes(), x.device)
-        L.check(self.lib.tsg_stem3_conv_fwd(x.data_ptr(), weight.data_ptr(), y.data_ptr(), B, H, W, ws.data_ptr(),
-                                            ws.numel(), L.stream_ptr(x)), "tsg_stem3_conv_fwd")
+        L.call(self.lib.tsg_stem3_conv_fwd, x.data_ptr(), weight.data_ptr(), y.data_ptr(), B, H, W, ws.data_ptr(), ws.numel(),
+               L.stream_ptr(x))
         return y
 
     def stem3_conv_wrw(self, x, dy):
@@ -476,8 +447,8 @@ class HipKernels:
             raise ValueError("stem3_conv_wrw: gradient shape %s does not match the image %s" % (tuple(dy.shape), tuple(x.shape)))
         dw = torch.empty((64, 3, 3, 3), dtype=torch.float32, device=x.device)
         ws = self._scratch("stem3", self.lib.tsg_stem3_conv_ws_bytes(), x.device)
-        L.check(self.lib.tsg_stem3_conv_wrw(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, H, W, ws.data_ptr(),
-                                            ws.numel(), L.stream_ptr(x)), "tsg_stem3_conv_wrw")
+        L.call(self.lib.tsg_stem3_conv_wrw, x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, H, W, ws.data_ptr(), ws.numel(),
+               L.stream_ptr(x))
         return dw
 
     def stem_conv_wrw_bn(self, x, da, xc, bp):
@@ -492,8 +463,8 @@ class HipKernels:
         B, _, H, W = x.shape
         dw = torch.empty((64, 3, 7, 7), dtype=torch.float32, device=x.device)
         ws = self._stem_ws(x.device)
-        L.check(self.lib.tsg_stem_conv_wrw_bn(x.data_ptr(), da.data_ptr(), xc.data_ptr(), bp.data_ptr(), dw.data_ptr(), B, H,
-                                              W, ws.data_ptr(), ws.numel(), L.stream_ptr(x)), "tsg_stem_conv_wrw_bn")
+        L.call(self.lib.tsg_stem_conv_wrw_bn, x.data_ptr(), da.data_ptr(), xc.data_ptr(), bp.data_ptr(), dw.data_ptr(), B, H, W,
+               ws.data_ptr(), ws.numel(), L.stream_ptr(x))
         return dw
 
     # ---- the recomputing ResNet stem (round 6): conv1 -> bn1 -> relu -> maxpool without the stem activation ----
@@ -501,12 +472,11 @@ class HipKernels:
         """-> partial fp32 [S,2,64] = {sum y, sum y^2} of y = stem_conv_fwd(x, weight), y not written"""
         _require_contiguous(x, weight)
         B, _, H, W = x.shape
-        S = self._count(("stem_stats", B, H, W), lambda: self.lib.tsg_stem_conv_stats_partials(B, H, W),
-                        "tsg_stem_conv_stats_partials")
+        S = self._count(self.lib.tsg_stem_conv_stats_partials, B, H, W)
         partial = torch.empty((S, 2, 64), dtype=torch.float32, device=x.device)
         ws = self._stem_ws(x.device)
-        L.check(self.lib.tsg_stem_conv_stats(x.data_ptr(), weight.data_ptr(), partial.data_ptr(), B, H, W, ws.data_ptr(),
-                                             ws.numel(), L.stream_ptr(x)), "tsg_stem_conv_stats")
+        L.call(self.lib.tsg_stem_conv_stats, x.data_ptr(), weight.data_ptr(), partial.data_ptr(), B, H, W, ws.data_ptr(),
+               ws.numel(), L.stream_ptr(x))
         return partial
 
     def stem_conv_bn_relu_pool_fwd(self, x, weight, fp):
@@ -518,9 +488,8 @@ class HipKernels:
         y = torch.empty((B, 64, PH, PW), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
         idx = torch.empty((B, PH, PW, 64), dtype=torch.uint8, device=x.device)
         ws = self._stem_ws(x.device)
-        L.check(self.lib.tsg_stem_conv_bn_relu_pool_fwd(x.data_ptr(), weight.data_ptr(), fp.data_ptr(), y.data_ptr(),
-                                                        idx.data_ptr(), B, H, W, ws.data_ptr(), ws.numel(), L.stream_ptr(x)),
-                "tsg_stem_conv_bn_relu_pool_fwd")
+        L.call(self.lib.tsg_stem_conv_bn_relu_pool_fwd, x.data_ptr(), weight.data_ptr(), fp.data_ptr(), y.data_ptr(),
+               idx.data_ptr(), B, H, W, ws.data_ptr(), ws.numel(), L.stream_ptr(x))
         return y, idx
 
     def stem_conv_bn_relu_pool_bwd_reduce(self, x, weight, dpool, idx, fp):
@@ -529,14 +498,11 @@ class HipKernels:
         if not dpool.is_contiguous(memory_format=torch.channels_last) or dpool.dtype != torch.bfloat16:
             raise ValueError("stem_conv_bn_relu_pool_bwd_reduce expects a bf16 channels_last pooled gradient")
         B, _, H, W = x.shape
-        S = self._count(("stem_pool", B, H, W), lambda: self.lib.tsg_stem_pool_bwd_num_partials(B, H, W),
-                        "tsg_stem_pool_bwd_num_partials")
+        S = self._count(self.lib.tsg_stem_pool_bwd_num_partials, B, H, W)
         partial = torch.empty((S, 2, 64), dtype=torch.float32, device=x.device)
         ws = self._stem_ws(x.device)
-        L.check(self.lib.tsg_stem_conv_bn_relu_pool_bwd_reduce(x.data_ptr(), weight.data_ptr(), dpool.data_ptr(), idx.data_ptr(),
-                                                               fp.data_ptr(), partial.data_ptr(), B, H, W, ws.data_ptr(),
-                                                               ws.numel(), L.stream_ptr(x)),
-                "tsg_stem_conv_bn_relu_pool_bwd_reduce")
+        L.call(self.lib.tsg_stem_conv_bn_relu_pool_bwd_reduce, x.data_ptr(), weight.data_ptr(), dpool.data_ptr(),
+               idx.data_ptr(), fp.data_ptr(), partial.data_ptr(), B, H, W, ws.data_ptr(), ws.numel(), L.stream_ptr(x))
         return partial, S
 
     def stem_conv_wrw_bn_pool(self, x, weight, dpool, idx, bp, xc=None):
@@ -553,9 +519,9 @@ class HipKernels:
             raise ValueError("stem_conv_wrw_bn_pool expects xc = the bf16 channels_last stem output")
         dw = torch.empty((64, 3, 7, 7), dtype=torch.float32, device=x.device)
         ws = self._stem_ws(x.device)
-        L.check(self.lib.tsg_stem_conv_wrw_bn_pool(x.data_ptr(), weight.data_ptr(), xc.data_ptr() if xc is not None else None,
-                                                   dpool.data_ptr(), idx.data_ptr(), bp.data_ptr(), dw.data_ptr(), B, H, W,
-                                                   ws.data_ptr(), ws.numel(), L.stream_ptr(x)), "tsg_stem_conv_wrw_bn_pool")
+        L.call(self.lib.tsg_stem_conv_wrw_bn_pool, x.data_ptr(), weight.data_ptr(), xc.data_ptr() if xc is not None else None,
+               dpool.data_ptr(), idx.data_ptr(), bp.data_ptr(), dw.data_ptr(), B, H, W, ws.data_ptr(), ws.numel(),
+               L.stream_ptr(x))
         return dw
 
     # ---- OHEM / focal / upsample ------------------------------------------
@@ -567,17 +533,15 @@ class HipKernels:
         P = B * HW
         dev = logits.device
         plan = L.OhemPlan()
-        L.check(self.lib.tsg_ohem_make_plan(B, Cc, HW, float(thresh), C.byref(plan)), "tsg_ohem_make_plan")
+        L.call(self.lib.tsg_ohem_make_plan, B, Cc, HW, float(thresh), C.byref(plan))
         ws = torch.empty(plan.ws_bytes, dtype=torch.uint8, device=dev)
         nll = torch.empty(P, dtype=torch.float32, device=dev)
         lse = torch.empty(P, dtype=torch.float32, device=dev)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         sel = torch.empty(8, dtype=torch.int32, device=dev)
-        L.check(self.lib.tsg_ohem_fwd(logits.data_ptr(), L.dtype_code(logits), labels.data_ptr(),
-                                      _label_code(labels), B, Cc, HW, int(ignore_label), float(thresh),
-                                      int(min_kept), L.ptr(weight), nll.data_ptr(), lse.data_ptr(),
-                                      loss.data_ptr(), sel.data_ptr(), ws.data_ptr(), plan.ws_bytes,
-                                      L.stream_ptr(logits)), "tsg_ohem_fwd")
+        L.call(self.lib.tsg_ohem_fwd, logits.data_ptr(), L.dtype_code(logits), labels.data_ptr(), _label_code(labels), B, Cc,
+               HW, int(ignore_label), float(thresh), int(min_kept), L.ptr(weight), nll.data_ptr(), lse.data_ptr(),
+               loss.data_ptr(), sel.data_ptr(), ws.data_ptr(), plan.ws_bytes, L.stream_ptr(logits))
         return loss, nll, lse, sel
 
     def ohem_bwd(self, logits, labels, ignore_label, weight, nll, lse, sel, gscale):
@@ -585,10 +549,9 @@ class HipKernels:
         B, Cc = logits.shape[0], logits.shape[1]
         HW = logits.numel() // (B * Cc)
         dlogits = torch.empty_like(logits)
-        L.check(self.lib.tsg_ohem_bwd(logits.data_ptr(), L.dtype_code(logits), labels.data_ptr(),
-                                      _label_code(labels), B, Cc, HW, int(ignore_label), L.ptr(weight),
-                                      nll.data_ptr(), lse.data_ptr(), sel.data_ptr(), gscale.data_ptr(),
-                                      dlogits.data_ptr(), None, L.stream_ptr(logits)), "tsg_ohem_bwd")
+        L.call(self.lib.tsg_ohem_bwd, logits.data_ptr(), L.dtype_code(logits), labels.data_ptr(), _label_code(labels), B, Cc,
+               HW, int(ignore_label), L.ptr(weight), nll.data_ptr(), lse.data_ptr(), sel.data_ptr(), gscale.data_ptr(),
+               dlogits.data_ptr(), None, L.stream_ptr(logits))
         return dlogits
 
     def ohem_up_supported(self, z, OH, OW, thresh):
@@ -601,17 +564,15 @@ class HipKernels:
         P = B * OH * OW
         dev = z.device
         plan = L.OhemPlan()
-        L.check(self.lib.tsg_ohem_make_plan(B, Cc, OH * OW, float(thresh), C.byref(plan)), "tsg_ohem_make_plan")
+        L.call(self.lib.tsg_ohem_make_plan, B, Cc, OH * OW, float(thresh), C.byref(plan))
         ws = torch.empty(plan.ws_bytes, dtype=torch.uint8, device=dev)
         nll = torch.empty(P, dtype=torch.float32, device=dev)
         lse = torch.empty(P, dtype=torch.float32, device=dev)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         sel = torch.empty(8, dtype=torch.int32, device=dev)
-        L.check(self.lib.tsg_ohem_up_fwd(z.data_ptr(), L.dtype_code(z), labels.data_ptr(), _label_code(labels),
-                                         B, Cc, IH, IW, int(OH), int(OW), int(ignore_label), float(thresh),
-                                         int(min_kept), L.ptr(weight), nll.data_ptr(), lse.data_ptr(),
-                                         loss.data_ptr(), sel.data_ptr(), ws.data_ptr(), plan.ws_bytes,
-                                         L.stream_ptr(z)), "tsg_ohem_up_fwd")
+        L.call(self.lib.tsg_ohem_up_fwd, z.data_ptr(), L.dtype_code(z), labels.data_ptr(), _label_code(labels), B, Cc, IH, IW,
+               int(OH), int(OW), int(ignore_label), float(thresh), int(min_kept), L.ptr(weight), nll.data_ptr(), lse.data_ptr(),
+               loss.data_ptr(), sel.data_ptr(), ws.data_ptr(), plan.ws_bytes, L.stream_ptr(z))
         return loss, nll, lse, sel
 
     def ohem_up_bwd(self, z, labels, OH, OW, ignore_label, weight, nll, lse, sel, gscale):
@@ -620,19 +581,17 @@ class HipKernels:
         dz = torch.empty_like(z)
         wsb = self.lib.tsg_ohem_up_bwd_ws_bytes(B, Cc, IH, int(OW))
         ws = torch.empty(wsb, dtype=torch.uint8, device=z.device)
-        L.check(self.lib.tsg_ohem_up_bwd(z.data_ptr(), L.dtype_code(z), labels.data_ptr(), _label_code(labels),
-                                         B, Cc, IH, IW, int(OH), int(OW), int(ignore_label), L.ptr(weight),
-                                         nll.data_ptr(), lse.data_ptr(), sel.data_ptr(), gscale.data_ptr(),
-                                         dz.data_ptr(), ws.data_ptr(), wsb, L.stream_ptr(z)), "tsg_ohem_up_bwd")
+        L.call(self.lib.tsg_ohem_up_bwd, z.data_ptr(), L.dtype_code(z), labels.data_ptr(), _label_code(labels), B, Cc, IH, IW,
+               int(OH), int(OW), int(ignore_label), L.ptr(weight), nll.data_ptr(), lse.data_ptr(), sel.data_ptr(),
+               gscale.data_ptr(), dz.data_ptr(), ws.data_ptr(), wsb, L.stream_ptr(z))
         return dz
 
     def ohem_target_prob(self, nll, labels, C_, ignore_label):
         """mask_prob (loss_opr.py:81-83) from the forward's nll, with the kernels' own exp: fp32 [P]"""
         _require_contiguous(nll, labels)
         out = torch.empty_like(nll)
-        L.check(self.lib.tsg_ohem_target_prob(nll.data_ptr(), labels.data_ptr(), _label_code(labels), nll.numel(),
-                                              int(C_), int(ignore_label), out.data_ptr(), L.stream_ptr(nll)),
-                "tsg_ohem_target_prob")
+        L.call(self.lib.tsg_ohem_target_prob, nll.data_ptr(), labels.data_ptr(), _label_code(labels), nll.numel(), int(C_),
+               int(ignore_label), out.data_ptr(), L.stream_ptr(nll))
         return out
 
     def kth_value(self, v, k):
@@ -640,8 +599,7 @@ class HipKernels:
         wsb = self.lib.tsg_kth_ws_bytes(n)
         ws = torch.empty(wsb, dtype=torch.uint8, device=v.device)
         out = torch.empty(1, dtype=torch.float32, device=v.device)
-        L.check(self.lib.tsg_kth_value(v.data_ptr(), n, int(k), out.data_ptr(), ws.data_ptr(), wsb,
-                                       L.stream_ptr(v)), "tsg_kth_value")
+        L.call(self.lib.tsg_kth_value, v.data_ptr(), n, int(k), out.data_ptr(), ws.data_ptr(), wsb, L.stream_ptr(v))
         return out
 
     def focal_fwd(self, pred, target, ignore_label, gamma, alpha):
@@ -650,18 +608,15 @@ class HipKernels:
         wsb = self.lib.tsg_focal_ws_bytes(P)
         ws = torch.empty(wsb, dtype=torch.uint8, device=pred.device)
         loss = torch.empty(1, dtype=torch.float32, device=pred.device)
-        L.check(self.lib.tsg_focal_fwd(pred.data_ptr(), L.dtype_code(pred), target.data_ptr(),
-                                       _label_code(target), P, int(ignore_label), float(gamma),
-                                       float(alpha), loss.data_ptr(), ws.data_ptr(), wsb,
-                                       L.stream_ptr(pred)), "tsg_focal_fwd")
+        L.call(self.lib.tsg_focal_fwd, pred.data_ptr(), L.dtype_code(pred), target.data_ptr(), _label_code(target), P,
+               int(ignore_label), float(gamma), float(alpha), loss.data_ptr(), ws.data_ptr(), wsb, L.stream_ptr(pred))
         return loss
 
     def focal_bwd(self, pred, target, ignore_label, gamma, alpha, gscale):
         dpred = torch.empty_like(pred)
-        L.check(self.lib.tsg_focal_bwd(pred.data_ptr(), L.dtype_code(pred), target.data_ptr(),
-                                       _label_code(target), pred.numel(), int(ignore_label), float(gamma),
-                                       float(alpha), gscale.data_ptr(), dpred.data_ptr(),
-                                       L.stream_ptr(pred)), "tsg_focal_bwd")
+        L.call(self.lib.tsg_focal_bwd, pred.data_ptr(), L.dtype_code(pred), target.data_ptr(), _label_code(target),
+               pred.numel(), int(ignore_label), float(gamma), float(alpha), gscale.data_ptr(), dpred.data_ptr(),
+               L.stream_ptr(pred))
         return dpred
 
     def upsample_fwd(self, x, add, OH, OW):
@@ -669,9 +624,8 @@ class HipKernels:
         _require_contiguous(x, add)
         N, Cc, IH, IW = x.shape
         y = torch.empty((N, Cc, OH, OW), dtype=x.dtype, device=x.device)
-        L.check(self.lib.tsg_upsample_bilinear_ac_fwd(x.data_ptr(), L.ptr(add), y.data_ptr(),
-                                                      L.dtype_code(x), N * Cc, IH, IW, OH, OW,
-                                                      L.stream_ptr(x)), "tsg_upsample_bilinear_ac_fwd")
+        L.call(self.lib.tsg_upsample_bilinear_ac_fwd, x.data_ptr(), L.ptr(add), y.data_ptr(), L.dtype_code(x), N * Cc, IH, IW,
+               OH, OW, L.stream_ptr(x))
         return y
 
     def upsample_presum_fwd(self, x, x2, OH, OW):
@@ -684,42 +638,37 @@ class HipKernels:
             raise L.TsgError("upsample_presum_fwd: the two addends must share shape, dtype and a dense layout")
         if x.is_contiguous():
             y = torch.empty((N, Cc, OH, OW), dtype=x.dtype, device=x.device)
-            L.check(self.lib.tsg_upsample_bilinear_ac_presum_fwd(x.data_ptr(), x2.data_ptr(), y.data_ptr(),
-                                                                 L.dtype_code(x), N * Cc, IH, IW, OH, OW,
-                                                                 L.stream_ptr(x)), "tsg_upsample_bilinear_ac_presum_fwd")
+            L.call(self.lib.tsg_upsample_bilinear_ac_presum_fwd, x.data_ptr(), x2.data_ptr(), y.data_ptr(), L.dtype_code(x),
+                   N * Cc, IH, IW, OH, OW, L.stream_ptr(x))
             return y
         if not x.is_contiguous(memory_format=torch.channels_last):
             raise L.TsgError("upsample_presum_fwd: dense NCHW or channels_last tensors only")
         y = torch.empty((N, Cc, OH, OW), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-        L.check(self.lib.tsg_upsample_bilinear_ac_nhwc_presum_fwd(x.data_ptr(), x2.data_ptr(), y.data_ptr(),
-                                                                  L.dtype_code(x), N, Cc, IH, IW, OH, OW,
-                                                                  L.stream_ptr(x)), "tsg_upsample_bilinear_ac_nhwc_presum_fwd")
+        L.call(self.lib.tsg_upsample_bilinear_ac_nhwc_presum_fwd, x.data_ptr(), x2.data_ptr(), y.data_ptr(), L.dtype_code(x), N,
+               Cc, IH, IW, OH, OW, L.stream_ptr(x))
         return y
 
     def upsample_bwd(self, dy, IH, IW):
         _require_contiguous(dy)
         N, Cc, OH, OW = dy.shape
         dx = torch.empty((N, Cc, IH, IW), dtype=dy.dtype, device=dy.device)
-        L.check(self.lib.tsg_upsample_bilinear_ac_bwd(dy.data_ptr(), dx.data_ptr(), L.dtype_code(dy),
-                                                      N * Cc, IH, IW, OH, OW, L.stream_ptr(dy)),
-                "tsg_upsample_bilinear_ac_bwd")
+        L.call(self.lib.tsg_upsample_bilinear_ac_bwd, dy.data_ptr(), dx.data_ptr(), L.dtype_code(dy), N * Cc, IH, IW, OH, OW,
+               L.stream_ptr(dy))
         return dx
 
     def upsample_fwd_nhwc(self, x, add, OH, OW):
         """x [N,C,IH,IW] channels_last-dense -> [N,C,OH,OW] channels_last"""
         N, Cc, IH, IW = x.shape
         y = torch.empty((N, Cc, OH, OW), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-        L.check(self.lib.tsg_upsample_bilinear_ac_nhwc_fwd(x.data_ptr(), L.ptr(add), y.data_ptr(),
-                                                           L.dtype_code(x), N, Cc, IH, IW, OH, OW,
-                                                           L.stream_ptr(x)), "tsg_upsample_bilinear_ac_nhwc_fwd")
+        L.call(self.lib.tsg_upsample_bilinear_ac_nhwc_fwd, x.data_ptr(), L.ptr(add), y.data_ptr(), L.dtype_code(x), N, Cc, IH,
+               IW, OH, OW, L.stream_ptr(x))
         return y
 
     def upsample_bwd_nhwc(self, dy, IH, IW):
         N, Cc, OH, OW = dy.shape
         dx = torch.empty((N, Cc, IH, IW), dtype=dy.dtype, device=dy.device, memory_format=torch.channels_last)
-        L.check(self.lib.tsg_upsample_bilinear_ac_nhwc_bwd(dy.data_ptr(), dx.data_ptr(), L.dtype_code(dy),
-                                                           N, Cc, IH, IW, OH, OW, L.stream_ptr(dy)),
-                "tsg_upsample_bilinear_ac_nhwc_bwd")
+        L.call(self.lib.tsg_upsample_bilinear_ac_nhwc_bwd, dy.data_ptr(), dx.data_ptr(), L.dtype_code(dy), N, Cc, IH, IW, OH,
+               OW, L.stream_ptr(dy))
         return dx
 
     def upsample_nearest(self, x, OH, OW):
@@ -727,9 +676,8 @@ class HipKernels:
         IH, IW = shp[-2], shp[-1]
         NC = x.numel() // (IH * IW)
         y = torch.empty(tuple(shp[:-2]) + (OH, OW), dtype=x.dtype, device=x.device)
-        L.check(self.lib.tsg_upsample_nearest_fwd(x.data_ptr(), y.data_ptr(), x.element_size(), NC,
-                                                  IH, IW, OH, OW, L.stream_ptr(x)),
-                "tsg_upsample_nearest_fwd")
+        L.call(self.lib.tsg_upsample_nearest_fwd, x.data_ptr(), y.data_ptr(), x.element_size(), NC, IH, IW, OH, OW,
+               L.stream_ptr(x))
         return y
 
 
@@ -744,8 +692,8 @@ class HipKernels:
         ws = torch.empty(wsb, dtype=torch.uint8, device=X.device)
         out = torch.empty((B, Cx, N), dtype=X.dtype, device=X.device)
         lse = torch.empty((B, N), dtype=torch.float32, device=X.device)
-        L.check(self.lib.tsg_psa_fwd(X.data_ptr(), A.data_ptr(), out.data_ptr(), lse.data_ptr(), dt, B, Cx,
-                                     Kd, N, ws.data_ptr(), wsb, L.stream_ptr(X)), "tsg_psa_fwd")
+        L.call(self.lib.tsg_psa_fwd, X.data_ptr(), A.data_ptr(), out.data_ptr(), lse.data_ptr(), dt, B, Cx, Kd, N,
+               ws.data_ptr(), wsb, L.stream_ptr(X))
         return out, lse
 
     def psa_bwd(self, X, A, out, dout, lse):
@@ -757,9 +705,8 @@ class HipKernels:
         ws = torch.empty(wsb, dtype=torch.uint8, device=X.device)
         dX = torch.empty_like(X)
         dA = torch.empty_like(A)
-        L.check(self.lib.tsg_psa_bwd(X.data_ptr(), A.data_ptr(), out.data_ptr(), dout.data_ptr(),
-                                     lse.data_ptr(), dX.data_ptr(), dA.data_ptr(), dt, B, Cx, Kd, N,
-                                     ws.data_ptr(), wsb, L.stream_ptr(X)), "tsg_psa_bwd")
+        L.call(self.lib.tsg_psa_bwd, X.data_ptr(), A.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), dX.data_ptr(),
+               dA.data_ptr(), dt, B, Cx, Kd, N, ws.data_ptr(), wsb, L.stream_ptr(X))
         return dX, dA
 
     # ---- classifier convolution of a head (csrc/clshead.hip) ---------------------
@@ -783,8 +730,7 @@ class HipKernels:
         Cout = weight.shape[0]
         x, w = self._rows(x), self._rows(weight)
         y = torch.empty((B, Cout, 1, 1), dtype=torch.bfloat16, device=x.device)
-        L.check(self.lib.tsg_conv1x1_vec_fwd(x.data_ptr(), w.data_ptr(), y.data_ptr(), B, Cin, Cout, L.stream_ptr(x)),
-                "tsg_conv1x1_vec_fwd")
+        L.call(self.lib.tsg_conv1x1_vec_fwd, x.data_ptr(), w.data_ptr(), y.data_ptr(), B, Cin, Cout, L.stream_ptr(x))
         return y
 
     def conv1x1_vec_bnact_fwd(self, x, weight, bnmode, act, gamma=None, beta=None, running_mean=None, running_var=None,
@@ -797,10 +743,9 @@ class HipKernels:
         out = torch.empty((B, Cout, 1, 1), dtype=torch.bfloat16, device=x.device)
         yc = torch.empty((B, Cout), dtype=torch.bfloat16, device=x.device) if bnmode else None
         stats = torch.empty((4, Cout), dtype=torch.float32, device=x.device) if bnmode else None
-        L.check(self.lib.tsg_conv1x1_vec_bnact_fwd(x.data_ptr(), w.data_ptr(), out.data_ptr(), L.ptr(yc), L.ptr(stats),
-                                                   L.ptr(gamma), L.ptr(beta), L.ptr(running_mean), L.ptr(running_var),
-                                                   L.ptr(num_batches_tracked), float(eps), float(momentum), int(bnmode),
-                                                   int(act), B, Cin, Cout, L.stream_ptr(x)), "tsg_conv1x1_vec_bnact_fwd")
+        L.call(self.lib.tsg_conv1x1_vec_bnact_fwd, x.data_ptr(), w.data_ptr(), out.data_ptr(), L.ptr(yc), L.ptr(stats),
+               L.ptr(gamma), L.ptr(beta), L.ptr(running_mean), L.ptr(running_var), L.ptr(num_batches_tracked), float(eps),
+               float(momentum), int(bnmode), int(act), B, Cin, Cout, L.stream_ptr(x))
         return out, yc, stats
 
     def conv1x1_vec_bnact_bwd(self, dout, out, yc, stats, x, weight, bnmode, act, need_dx=True):
@@ -812,10 +757,9 @@ class HipKernels:
         dw = torch.empty((Cout, Cin, 1, 1), dtype=torch.float32, device=x.device)
         dgamma = torch.empty(Cout, dtype=torch.float32, device=x.device) if bnmode else None
         dbeta = torch.empty(Cout, dtype=torch.float32, device=x.device) if bnmode else None
-        L.check(self.lib.tsg_conv1x1_vec_bnact_bwd(dout.data_ptr(), out.data_ptr(), L.ptr(yc), L.ptr(stats), x.data_ptr(),
-                                                   w.data_ptr(), L.ptr(dx), dw.data_ptr(), L.ptr(dgamma), L.ptr(dbeta),
-                                                   int(bnmode), int(act), B, Cin, Cout, L.stream_ptr(x)),
-                "tsg_conv1x1_vec_bnact_bwd")
+        L.call(self.lib.tsg_conv1x1_vec_bnact_bwd, dout.data_ptr(), out.data_ptr(), L.ptr(yc), L.ptr(stats), x.data_ptr(),
+               w.data_ptr(), L.ptr(dx), dw.data_ptr(), L.ptr(dgamma), L.ptr(dbeta), int(bnmode), int(act), B, Cin, Cout,
+               L.stream_ptr(x))
         return dx, dw, dgamma, dbeta
 
     def conv1x1_vec_bwd(self, dy, x, weight, need_dx=True):
@@ -825,8 +769,8 @@ class HipKernels:
         dy, x, w = self._rows(dy), self._rows(x), self._rows(weight)
         dx = torch.empty((B, Cin, 1, 1), dtype=torch.bfloat16, device=x.device) if need_dx else None
         dw = torch.empty((Cout, Cin, 1, 1), dtype=torch.float32, device=x.device)
-        L.check(self.lib.tsg_conv1x1_vec_bwd(dy.data_ptr(), x.data_ptr(), w.data_ptr(), L.ptr(dx), dw.data_ptr(), B, Cin, Cout,
-                                             L.stream_ptr(x)), "tsg_conv1x1_vec_bwd")
+        L.call(self.lib.tsg_conv1x1_vec_bwd, dy.data_ptr(), x.data_ptr(), w.data_ptr(), L.ptr(dx), dw.data_ptr(), B, Cin, Cout,
+               L.stream_ptr(x))
         return dx, dw
 
     def cls_head_supported(self, x, weight):
@@ -842,8 +786,8 @@ class HipKernels:
         B, Cc, H, W = x.shape
         N = weight.shape[0]
         z = torch.empty((B, N, H, W), dtype=torch.bfloat16, device=x.device)
-        L.check(self.lib.tsg_cls_head_fwd(x.data_ptr(), weight.data_ptr(), L.ptr(bias), z.data_ptr(), B, H * W, Cc, N,
-                                          L.stream_ptr(x)), "tsg_cls_head_fwd")
+        L.call(self.lib.tsg_cls_head_fwd, x.data_ptr(), weight.data_ptr(), L.ptr(bias), z.data_ptr(), B, H * W, Cc, N,
+               L.stream_ptr(x))
         return z
 
     def cls_head_bwd(self, dz, x, weight, need_dx=True, need_db=True):
@@ -854,14 +798,14 @@ class HipKernels:
         dx = None
         if need_dx:
             dx = torch.empty_like(x)
-            L.check(self.lib.tsg_cls_head_dgrad(dz.data_ptr(), weight.data_ptr(), dx.data_ptr(), B, H * W, Cc, N,
-                                                L.stream_ptr(dz)), "tsg_cls_head_dgrad")
+            L.call(self.lib.tsg_cls_head_dgrad, dz.data_ptr(), weight.data_ptr(), dx.data_ptr(), B, H * W, Cc, N,
+                   L.stream_ptr(dz))
         dw = torch.empty_like(weight)
         db = torch.empty(N, dtype=torch.float32, device=x.device) if need_db else None
         wsb = self.lib.tsg_cls_head_wgrad_ws_bytes(B, Cc, N)
         ws = torch.empty(wsb, dtype=torch.uint8, device=x.device)
-        L.check(self.lib.tsg_cls_head_wgrad(dz.data_ptr(), x.data_ptr(), dw.data_ptr(), L.ptr(db), B, H * W, Cc, N,
-                                            ws.data_ptr(), wsb, L.stream_ptr(dz)), "tsg_cls_head_wgrad")
+        L.call(self.lib.tsg_cls_head_wgrad, dz.data_ptr(), x.data_ptr(), dw.data_ptr(), L.ptr(db), B, H * W, Cc, N,
+               ws.data_ptr(), wsb, L.stream_ptr(dz))
         return dx, dw, db
 
     # ---- reference-accuracy fp32 convolution (parity path; csrc/convf32.hip) ------
@@ -879,20 +823,18 @@ class HipKernels:
         cl = x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous()
         y = torch.empty((B, Cout, OH, OW), dtype=torch.float32, device=x.device,
                         memory_format=torch.channels_last if cl else torch.contiguous_format)
-        L.check(self.lib.tsg_conv2d_f32_exact_fwd(x.data_ptr(), w.data_ptr(), y.data_ptr(), B, Cin, H, W, Cout, KH, KW,
-                                                  stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1],
-                                                  self._strides4(x), self._strides4(w), self._strides4(y),
-                                                  L.stream_ptr(x)), "tsg_conv2d_f32_exact_fwd")
+        L.call(self.lib.tsg_conv2d_f32_exact_fwd, x.data_ptr(), w.data_ptr(), y.data_ptr(), B, Cin, H, W, Cout, KH, KW,
+               stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1], self._strides4(x), self._strides4(w),
+               self._strides4(y), L.stream_ptr(x))
         return y
 
     def conv2d_f32_exact_dgrad(self, dy, w, x_like, stride, padding, dilation):
         B, Cin, H, W = x_like.shape
         Cout, _, KH, KW = w.shape
         dx = torch.empty_like(x_like)
-        L.check(self.lib.tsg_conv2d_f32_exact_dgrad(dy.data_ptr(), w.data_ptr(), dx.data_ptr(), B, Cin, H, W, Cout, KH, KW,
-                                                    stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1],
-                                                    self._strides4(dx), self._strides4(w), self._strides4(dy),
-                                                    L.stream_ptr(dy)), "tsg_conv2d_f32_exact_dgrad")
+        L.call(self.lib.tsg_conv2d_f32_exact_dgrad, dy.data_ptr(), w.data_ptr(), dx.data_ptr(), B, Cin, H, W, Cout, KH, KW,
+               stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1], self._strides4(dx), self._strides4(w),
+               self._strides4(dy), L.stream_ptr(dy))
         return dx
 
     def conv2d_f32_exact_wgrad(self, x, dy, w_like, stride, padding, dilation):
@@ -902,9 +844,8 @@ class HipKernels:
         geo = (Cin, H, W, Cout, KH, KW, stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1])
         wsb = self.lib.tsg_conv2d_f32_exact_wgrad_ws_bytes(B, *geo)
         ws = torch.empty(max(wsb, 8), dtype=torch.uint8, device=x.device)
-        L.check(self.lib.tsg_conv2d_f32_exact_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, *geo,
-                                                    self._strides4(x), self._strides4(dw), self._strides4(dy),
-                                                    ws.data_ptr(), wsb, L.stream_ptr(x)), "tsg_conv2d_f32_exact_wgrad")
+        L.call(self.lib.tsg_conv2d_f32_exact_wgrad, x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, *geo, self._strides4(x),
+               self._strides4(dw), self._strides4(dy), ws.data_ptr(), wsb, L.stream_ptr(x))
         return dw
 
     # ---- depthwise 3x3 convolution (Xception39; csrc/dwconv.hip) ---------------
@@ -922,16 +863,16 @@ class HipKernels:
         B, Cc, H, W = x.shape
         y = torch.empty((B, Cc, (H - 1) // stride + 1, (W - 1) // stride + 1), dtype=x.dtype, device=x.device,
                         memory_format=torch.channels_last)
-        L.check(self.lib.tsg_dwconv3x3_fwd(x.data_ptr(), weight.data_ptr(), y.data_ptr(), L.dtype_code(x), B, H, W, Cc,
-                                           stride, L.stream_ptr(x)), "tsg_dwconv3x3_fwd")
+        L.call(self.lib.tsg_dwconv3x3_fwd, x.data_ptr(), weight.data_ptr(), y.data_ptr(), L.dtype_code(x), B, H, W, Cc, stride,
+               L.stream_ptr(x))
         return y
 
     def dwconv3x3_dgrad(self, dy, weight, x_like, stride):
         """dy [B,C,OH,OW] channels_last (x's dtype) -> dx shaped like x_like, channels_last"""
         B, Cc, H, W = x_like.shape
         dx = torch.empty((B, Cc, H, W), dtype=dy.dtype, device=dy.device, memory_format=torch.channels_last)
-        L.check(self.lib.tsg_dwconv3x3_dgrad(dy.data_ptr(), weight.data_ptr(), dx.data_ptr(), L.dtype_code(dy), B, H, W,
-                                             Cc, stride, L.stream_ptr(dy)), "tsg_dwconv3x3_dgrad")
+        L.call(self.lib.tsg_dwconv3x3_dgrad, dy.data_ptr(), weight.data_ptr(), dx.data_ptr(), L.dtype_code(dy), B, H, W, Cc,
+               stride, L.stream_ptr(dy))
         return dx
 
     def dwconv3x3_wgrad(self, x, dy, weight, stride):
@@ -943,20 +884,18 @@ class HipKernels:
             L.check(-3, "tsg_dwconv3x3_wgrad_ws_bytes")
         ws = torch.empty(wsb, dtype=torch.uint8, device=x.device)
         dw = torch.empty_like(weight)
-        L.check(self.lib.tsg_dwconv3x3_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), dt, B, H, W, Cc, stride,
-                                             ws.data_ptr(), wsb, L.stream_ptr(x)), "tsg_dwconv3x3_wgrad")
+        L.call(self.lib.tsg_dwconv3x3_wgrad, x.data_ptr(), dy.data_ptr(), dw.data_ptr(), dt, B, H, W, Cc, stride, ws.data_ptr(),
+               wsb, L.stream_ptr(x))
         return dw
 
     def sgd_step(self, param, grad, buf, lr, momentum, weight_decay, grad_scale, first):
-        L.check(self.lib.tsg_sgd_step(param.data_ptr(), grad.data_ptr(), buf.data_ptr(), param.numel(),
-                                      float(lr), float(momentum), float(weight_decay), float(grad_scale),
-                                      int(first), L.stream_ptr(param)), "tsg_sgd_step")
+        L.call(self.lib.tsg_sgd_step, param.data_ptr(), grad.data_ptr(), buf.data_ptr(), param.numel(), float(lr),
+               float(momentum), float(weight_decay), float(grad_scale), int(first), L.stream_ptr(param))
 
 
     def sgd_step_dev(self, param, grad, buf, lr_dev, lr_mult, momentum, weight_decay, grad_scale=1.0):
-        L.check(self.lib.tsg_sgd_step_dev(param.data_ptr(), grad.data_ptr(), buf.data_ptr(), param.numel(),
-                                          lr_dev.data_ptr(), float(lr_mult), float(momentum), float(weight_decay),
-                                          float(grad_scale), L.stream_ptr(param)), "tsg_sgd_step_dev")
+        L.call(self.lib.tsg_sgd_step_dev, param.data_ptr(), grad.data_ptr(), buf.data_ptr(), param.numel(), lr_dev.data_ptr(),
+               float(lr_mult), float(momentum), float(weight_decay), float(grad_scale), L.stream_ptr(param))
 
     # ---- 3x3 weight gradient ----------------------------------------------------
     def conv3x3_c64_supported(self, x, weight, stride, padding, dilation, groups):
@@ -968,11 +907,7 @@ class HipKernels:
     def conv3x3_c64_bnsums_supported(self, B, H, W, stride):
         """can the 64 -> 64 data gradient of this input size emit the BatchNorm backward sums in its epilogue (`bsum=`)?"""
         fn = self.lib.tsg_conv3x3_c64_dgrad_bnsums_partials if stride == 1 else self.lib.tsg_conv3x3_c64_s2_dgrad_partials
-        key = ("c64_bsum", stride, B, H, W)
-        v = self._npart.get(key)
-        if v is None:
-            v = self._npart[key] = fn(B, H, W)
-        return v > 0
+        return self._count(fn, B, H, W, may_be_zero=True) > 0
 
     @staticmethod
     def _check_bsum(bsum, like_shape):
@@ -996,13 +931,11 @@ class HipKernels:
                 raise ValueError("conv3x3_c64_fwd: bsum goes with the plain stride-1 launch only")
             bx, fp = self._check_bsum(bsum, x.shape)
             B, _, H, W = x.shape
-            S = self._count(("c64_bsum", 1, B, H, W), lambda: self.lib.tsg_conv3x3_c64_dgrad_bnsums_partials(B, H, W),
-                            "tsg_conv3x3_c64_dgrad_bnsums_partials")
+            S = self._count(self.lib.tsg_conv3x3_c64_dgrad_bnsums_partials, B, H, W)
             y = torch.empty_like(x)
             partial = torch.empty((S, 2, 64), dtype=torch.float32, device=x.device)
-            L.check(self.lib.tsg_conv3x3_c64_dgrad_bnsums(x.data_ptr(), wb.data_ptr(), y.data_ptr(), bx.data_ptr(),
-                                                          fp.data_ptr(), partial.data_ptr(), B, H, W, L.stream_ptr(x)),
-                    "tsg_conv3x3_c64_dgrad_bnsums")
+            L.call(self.lib.tsg_conv3x3_c64_dgrad_bnsums, x.data_ptr(), wb.data_ptr(), y.data_ptr(), bx.data_ptr(),
+                   fp.data_ptr(), partial.data_ptr(), B, H, W, L.stream_ptr(x))
             return y, partial
         if in_ab is not None and (in_ab.dtype != torch.float32 or not in_ab.is_contiguous() or in_ab.shape[-1] != 64):
             raise ValueError("conv3x3_c64_fwd: in_ab must be a contiguous fp32 [>=2, 64] pack")
@@ -1012,27 +945,26 @@ class HipKernels:
         lib = self.lib
         if stride == 1:
             y = torch.empty_like(x)
-            fn, cnt, what = lib.tsg_conv3x3_c64_fwd, lib.tsg_conv3x3_c64_stats_partials, "tsg_conv3x3_c64_fwd"
+            fn, cnt = lib.tsg_conv3x3_c64_fwd, lib.tsg_conv3x3_c64_stats_partials
         else:
             y = torch.empty((B, 64, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=x.dtype, device=x.device,
                             memory_format=torch.channels_last)
-            fn, cnt, what = lib.tsg_conv3x3_c64_s2_fwd, lib.tsg_conv3x3_c64_s2_stats_partials, "tsg_conv3x3_c64_s2_fwd"
+            fn, cnt = lib.tsg_conv3x3_c64_s2_fwd, lib.tsg_conv3x3_c64_s2_stats_partials
         partial = None
         if with_stats:
-            S = self._count(("c64_stats", stride, B, H, W), lambda: cnt(B, H, W), what)
+            S = self._count(cnt, B, H, W)
             partial = torch.empty((S, 2, 64), dtype=torch.float32, device=x.device)
         if addend is not None:
             if stride != 1 or with_stats or addend.shape != y.shape or addend.dtype != y.dtype \
                     or not addend.is_contiguous(memory_format=torch.channels_last):
                 raise ValueError("conv3x3_c64_fwd: addend needs stride 1, no statistics, a bf16 channels_last tensor of y's shape")
-            L.check(fn(x.data_ptr(), wb.data_ptr(), y.data_ptr(), None, L.ptr(in_ab), addend.data_ptr(), B, H, W,
-                       L.stream_ptr(x)), what)
+            L.call(fn, x.data_ptr(), wb.data_ptr(), y.data_ptr(), None, L.ptr(in_ab), addend.data_ptr(), B, H, W,
+                   L.stream_ptr(x))
             return y
         if stride == 1:
-            L.check(fn(x.data_ptr(), wb.data_ptr(), y.data_ptr(), L.ptr(partial), L.ptr(in_ab), None, B, H, W,
-                       L.stream_ptr(x)), what)
+            L.call(fn, x.data_ptr(), wb.data_ptr(), y.data_ptr(), L.ptr(partial), L.ptr(in_ab), None, B, H, W, L.stream_ptr(x))
         else:
-            L.check(fn(x.data_ptr(), wb.data_ptr(), y.data_ptr(), L.ptr(partial), L.ptr(in_ab), B, H, W, L.stream_ptr(x)), what)
+            L.call(fn, x.data_ptr(), wb.data_ptr(), y.data_ptr(), L.ptr(partial), L.ptr(in_ab), B, H, W, L.stream_ptr(x))
         return (y, partial) if with_stats else y
 
     def conv3x3_gen_supported(self, x, weight, stride, padding, dilation, groups):
@@ -1044,8 +976,7 @@ class HipKernels:
 
     def conv3x3_gen_tile(self, B, H, W, Cin, Cout):
         """output channels per block (64 / 128) for this problem: the prepared filter is laid out for it"""
-        return self._count(("g3_tile", B, H, W, Cin, Cout), lambda: self.lib.tsg_conv3x3_gen_tile(B, H, W, Cin, Cout),
-                           "tsg_conv3x3_gen_tile")
+        return self._count(self.lib.tsg_conv3x3_gen_tile, B, H, W, Cin, Cout)
 
     def conv3x3_gen_variant(self, B, H, W, Cin, Cout, with_in_ab=False):
         """0: 8-row pixel tiles (conv3g_fwd_k), 1: 16-row tiles with all staging by LDS-DMA (conv3h_fwd_k)"""
@@ -1072,8 +1003,8 @@ class HipKernels:
             from .shadow import bank                  # a parameter: its prepared images are refreshed once per optimizer step
             return bank.get_gen(weight, int(mode), bn), bn
         out = torch.empty(9 * O * I, dtype=torch.bfloat16, device=weight.device)
-        L.check(self.lib.tsg_conv3x3_gen_prep_filter(weight.data_ptr(), L.dtype_code(weight), out.data_ptr(), O, I, int(mode),
-                                                     bn, L.stream_ptr(weight)), "tsg_conv3x3_gen_prep_filter")
+        L.call(self.lib.tsg_conv3x3_gen_prep_filter, weight.data_ptr(), L.dtype_code(weight), out.data_ptr(), O, I, int(mode),
+               bn, L.stream_ptr(weight))
         return out, bn
 
     def conv3x3_gen_fwd(self, x, wf, Cout, with_stats=False, in_ab=None, addend=None):
@@ -1094,12 +1025,10 @@ class HipKernels:
             raise ValueError("conv3x3_gen_fwd: addend must be a bf16 channels_last tensor of the output's shape (no statistics)")
         partial = None
         if with_stats:
-            S = self._count(("g3_stats", B, H, W, Cin, Cout, bn),
-                            lambda: self.lib.tsg_conv3x3_gen_stats_partials(B, H, W, Cin, Cout, bn),
-                            "tsg_conv3x3_gen_stats_partials")
+            S = self._count(self.lib.tsg_conv3x3_gen_stats_partials, B, H, W, Cin, Cout, bn)
             partial = torch.empty((S, 2, Cout), dtype=torch.float32, device=x.device)
-        L.check(self.lib.tsg_conv3x3_gen_fwd(x.data_ptr(), wf.data_ptr(), y.data_ptr(), L.ptr(partial), L.ptr(in_ab),
-                                             L.ptr(addend), B, H, W, Cin, Cout, bn, L.stream_ptr(x)), "tsg_conv3x3_gen_fwd")
+        L.call(self.lib.tsg_conv3x3_gen_fwd, x.data_ptr(), wf.data_ptr(), y.data_ptr(), L.ptr(partial), L.ptr(in_ab),
+               L.ptr(addend), B, H, W, Cin, Cout, bn, L.stream_ptr(x))
         return (y, partial) if with_stats else y
 
     # ---- dilated 3x3 convolutions (PSPNet / PSANet backbone; csrc/dilconv.hip) ---------------
@@ -1138,12 +1067,10 @@ class HipKernels:
             raise ValueError("conv3x3_dil_fwd: addend must be a bf16 channels_last tensor of the output's shape (no statistics)")
         partial = None
         if with_stats:
-            S = self._count(("dil_stats", B, H, W, Cin, Cout, dilation),
-                            lambda: self.lib.tsg_conv3x3_dil_stats_partials(B, H, W, Cin, Cout, int(dilation)),
-                            "tsg_conv3x3_dil_stats_partials")
+            S = self._count(self.lib.tsg_conv3x3_dil_stats_partials, B, H, W, Cin, Cout, int(dilation))
             partial = torch.empty((S, 2, Cout), dtype=torch.float32, device=x.device)
-        L.check(self.lib.tsg_conv3x3_dil_fwd(x.data_ptr(), wf.data_ptr(), y.data_ptr(), L.ptr(partial), L.ptr(addend), B, H, W,
-                                             Cin, Cout, int(dilation), L.stream_ptr(x)), "tsg_conv3x3_dil_fwd")
+        L.call(self.lib.tsg_conv3x3_dil_fwd, x.data_ptr(), wf.data_ptr(), y.data_ptr(), L.ptr(partial), L.ptr(addend), B, H, W,
+               Cin, Cout, int(dilation), L.stream_ptr(x))
         return (y, partial) if with_stats else y
 
     def conv3x3_dil_dgrad(self, dy, weight, dilation, addend=None):
@@ -1169,8 +1096,8 @@ class HipKernels:
         if wsb == 0:
             raise L.TsgError("conv3x3_dil_wrw: unsupported shape %s -> %d channels, dilation %d" % (tuple(x.shape), Cout, dilation))
         ws = self._scratch("c3d", wsb, x.device)                  # per stream, grown to the largest layer
-        L.check(self.lib.tsg_conv3x3_dil_wrw(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, H, W, Cin, Cout, int(dilation),
-                                             ws.data_ptr(), ws.numel(), L.stream_ptr(x)), "tsg_conv3x3_dil_wrw")
+        L.call(self.lib.tsg_conv3x3_dil_wrw, x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, H, W, Cin, Cout, int(dilation),
+               ws.data_ptr(), ws.numel(), L.stream_ptr(x))
         return dw
 
     def conv3x3_s2_dgrad_supported(self, Cin, Cout):
@@ -1197,11 +1124,11 @@ class HipKernels:
         wf, _ = self.conv3x3_gen_prep_filter(weight, 1, dy, bn=32)
         dx = torch.empty((B, Cin, H, W), dtype=torch.bfloat16, device=dy.device, memory_format=torch.channels_last)
         if addend_sub is not None:
-            L.check(self.lib.tsg_conv3x3_s2_dgrad_subadd(dy.data_ptr(), wf.data_ptr(), dx.data_ptr(), addend_sub.data_ptr(), B, H,
-                                                         W, Cin, Cout, L.stream_ptr(dy)), "tsg_conv3x3_s2_dgrad_subadd")
+            L.call(self.lib.tsg_conv3x3_s2_dgrad_subadd, dy.data_ptr(), wf.data_ptr(), dx.data_ptr(), addend_sub.data_ptr(), B,
+                   H, W, Cin, Cout, L.stream_ptr(dy))
             return dx
-        L.check(self.lib.tsg_conv3x3_s2_dgrad(dy.data_ptr(), wf.data_ptr(), dx.data_ptr(), L.ptr(addend), B, H, W, Cin, Cout,
-                                              L.stream_ptr(dy)), "tsg_conv3x3_s2_dgrad")
+        L.call(self.lib.tsg_conv3x3_s2_dgrad, dy.data_ptr(), wf.data_ptr(), dx.data_ptr(), L.ptr(addend), B, H, W, Cin, Cout,
+               L.stream_ptr(dy))
         return dx
 
     def conv3x3_c64_s2_dgrad(self, dy, wt, in_hw, bsum=None):
@@ -1216,15 +1143,12 @@ class HipKernels:
         dx = torch.empty((B, 64, H, W), dtype=dy.dtype, device=dy.device, memory_format=torch.channels_last)
         if bsum is not None:
             bx, fp = self._check_bsum(bsum, dx.shape)
-            S = self._count(("c64_bsum", 2, B, H, W), lambda: self.lib.tsg_conv3x3_c64_s2_dgrad_partials(B, H, W),
-                            "tsg_conv3x3_c64_s2_dgrad_partials")
+            S = self._count(self.lib.tsg_conv3x3_c64_s2_dgrad_partials, B, H, W)
             partial = torch.empty((S, 2, 64), dtype=torch.float32, device=dy.device)
-            L.check(self.lib.tsg_conv3x3_c64_s2_dgrad_bnsums(dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), bx.data_ptr(),
-                                                             fp.data_ptr(), partial.data_ptr(), B, H, W, L.stream_ptr(dy)),
-                    "tsg_conv3x3_c64_s2_dgrad_bnsums")
+            L.call(self.lib.tsg_conv3x3_c64_s2_dgrad_bnsums, dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), bx.data_ptr(),
+                   fp.data_ptr(), partial.data_ptr(), B, H, W, L.stream_ptr(dy))
             return dx, partial
-        L.check(self.lib.tsg_conv3x3_c64_s2_dgrad(dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), B, H, W, L.stream_ptr(dy)),
-                "tsg_conv3x3_c64_s2_dgrad")
+        L.call(self.lib.tsg_conv3x3_c64_s2_dgrad, dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), B, H, W, L.stream_ptr(dy))
         return dx
 
     def conv3x3_wrw_supported(self, x, weight, stride, padding, dilation, groups):
@@ -1262,23 +1186,21 @@ class HipKernels:
             fn = self.lib.tsg_conv3x3_wrw_tr if variant == "tr" else self.lib.tsg_conv3x3_wrw
             ws = self._scratch("c3", self.lib.tsg_conv3x3_wrw_ws_bytes(), x.device)
             if in_ab is not None:
-                L.check(self.lib.tsg_conv3x3_wrw_tr_norm(x.data_ptr(), in_ab.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, H, W,
-                                                         ws.data_ptr(), ws.numel(), L.stream_ptr(x)), "tsg_conv3x3_wrw_tr_norm")
+                L.call(self.lib.tsg_conv3x3_wrw_tr_norm, x.data_ptr(), in_ab.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, H, W,
+                       ws.data_ptr(), ws.numel(), L.stream_ptr(x))
             else:
-                L.check(fn(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, H, W, ws.data_ptr(), ws.numel(), L.stream_ptr(x)),
-                        "tsg_conv3x3_wrw")
+                L.call(fn, x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, H, W, ws.data_ptr(), ws.numel(), L.stream_ptr(x))
             return dw
         wsb = self.lib.tsg_conv3x3_wrw_gen_ws_bytes(B, H, W, Cin, Cout, stride)
         if wsb == 0:
             raise L.TsgError("conv3x3_wrw: unsupported shape %s -> %d channels, stride %d" % (tuple(x.shape), Cout, stride))
         ws = self._scratch("c3g", wsb, x.device)                  # per stream, grown to the largest layer (<= 38 MB)
         if in_ab is not None:
-            L.check(self.lib.tsg_conv3x3_wrw_gen_norm(x.data_ptr(), in_ab.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, H, W, Cin,
-                                                      Cout, int(stride), ws.data_ptr(), ws.numel(), L.stream_ptr(x)),
-                    "tsg_conv3x3_wrw_gen_norm")
+            L.call(self.lib.tsg_conv3x3_wrw_gen_norm, x.data_ptr(), in_ab.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, H, W,
+                   Cin, Cout, int(stride), ws.data_ptr(), ws.numel(), L.stream_ptr(x))
         else:
-            L.check(self.lib.tsg_conv3x3_wrw_gen(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, H, W, Cin, Cout, int(stride),
-                                                 ws.data_ptr(), ws.numel(), L.stream_ptr(x)), "tsg_conv3x3_wrw_gen")
+            L.call(self.lib.tsg_conv3x3_wrw_gen, x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, H, W, Cin, Cout, int(stride),
+                   ws.data_ptr(), ws.numel(), L.stream_ptr(x))
         return dw
 
     def conv3x3_weight_rot180_t(self, w):
@@ -1287,8 +1209,7 @@ class HipKernels:
             raise L.TsgError("conv3x3_weight_rot180_t takes a channels_last [O, I, 3, 3] filter")
         O, I = w.shape[0], w.shape[1]
         out = torch.empty((I, O, 3, 3), dtype=torch.bfloat16, device=w.device, memory_format=torch.channels_last)
-        L.check(self.lib.tsg_conv3x3_weight_rot180_t(w.data_ptr(), L.dtype_code(w), out.data_ptr(), O, I, L.stream_ptr(w)),
-                "tsg_conv3x3_weight_rot180_t")
+        L.call(self.lib.tsg_conv3x3_weight_rot180_t, w.data_ptr(), L.dtype_code(w), out.data_ptr(), O, I, L.stream_ptr(w))
         return out
 
     # ---- training pre-processing ---------------------------------------------------
@@ -1317,13 +1238,10 @@ class HipKernels:
             k = min(cap, n - i0)
             pi = (C.c_void_p * k)(*[imgs[i0 + j].data_ptr() for j in range(k)])
             pg = (C.c_void_p * k)(*[gts[i0 + j].data_ptr() for j in range(k)]) if gts is not None else None
-            L.check(self.lib.tsg_augment_crop(pi, pg, geom[i0:i0 + k].ctypes.data,
-                                              inv_scale[i0:i0 + k].ctypes.data if inv_scale is not None else None,
-                                              k, CH, CW, m.ctypes.data, s.ctypes.data,
-                                              float(pad_pixel), int(pad_label), out[i0:].data_ptr(),
-                                              lab[i0:].data_ptr() if lab is not None else None,
-                                              _label_code(lab) if lab is not None else L.I64,
-                                              L.stream_ptr(out)), "tsg_augment_crop")
+            L.call(self.lib.tsg_augment_crop, pi, pg, geom[i0:i0 + k].ctypes.data,
+                   inv_scale[i0:i0 + k].ctypes.data if inv_scale is not None else None, k, CH, CW, m.ctypes.data, s.ctypes.data,
+                   float(pad_pixel), int(pad_label), out[i0:].data_ptr(), lab[i0:].data_ptr() if lab is not None else None,
+                   _label_code(lab) if lab is not None else L.I64, L.stream_ptr(out))
         return out, lab
 
     def edge_labels(self, gts, geom, crop_hw, ignore_label=255, threshold=5, aperture=7, dilate_size=7, pad_label=255,
@@ -1341,10 +1259,9 @@ class HipKernels:
                 raise L.TsgError("edge_labels takes contiguous uint8 tensors on the GPU")
             wsb = self.lib.tsg_edge_labels_ws_bytes(int(geom[i, 2]), int(geom[i, 3]))
             ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-            L.check(self.lib.tsg_edge_labels(gts[i].data_ptr(), geom[i].ctypes.data, None, CH, CW, int(ignore_label),
-                                             int(threshold), int(threshold), int(aperture), int(dilate_size), int(pad_label),
-                                             out[i].data_ptr(), _label_code(out), ws.data_ptr(), wsb, L.stream_ptr(out)),
-                    "tsg_edge_labels")
+            L.call(self.lib.tsg_edge_labels, gts[i].data_ptr(), geom[i].ctypes.data, None, CH, CW, int(ignore_label),
+                   int(threshold), int(threshold), int(aperture), int(dilate_size), int(pad_label), out[i].data_ptr(),
+                   _label_code(out), ws.data_ptr(), wsb, L.stream_ptr(out))
         return out
 
     def resize_bilinear_hp(self, x, OH, OW, out=None, accumulate=False):
@@ -1355,8 +1272,8 @@ class HipKernels:
         if out is None:
             out = torch.empty(tuple(x.shape[:-2]) + (OH, OW), dtype=torch.float32, device=x.device)
             accumulate = False
-        L.check(self.lib.tsg_resize_bilinear_hp(x.data_ptr(), out.data_ptr(), L.dtype_code(x), NC, IH, IW, int(OH), int(OW),
-                                                int(accumulate), L.stream_ptr(x)), "tsg_resize_bilinear_hp")
+        L.call(self.lib.tsg_resize_bilinear_hp, x.data_ptr(), out.data_ptr(), L.dtype_code(x), NC, IH, IW, int(OH), int(OW),
+               int(accumulate), L.stream_ptr(x))
         return out
 
     # ---- segmentation head tail (evaluation) -----------------------------------
@@ -1370,8 +1287,7 @@ class HipKernels:
             raise L.TsgError(f"seg_tail_logprob: unsupported shape {tuple(z.shape)} -> ({H}, {W})")
         if out is None:
             out = torch.empty((N, Cc, int(H), int(W)), dtype=torch.float32, device=z.device)
-        L.check(self.lib.tsg_seg_tail_logprob(z.data_ptr(), dt, N, Cc, h, w, int(H), int(W), out.data_ptr(),
-                                              L.stream_ptr(z)), "tsg_seg_tail_logprob")
+        L.call(self.lib.tsg_seg_tail_logprob, z.data_ptr(), dt, N, Cc, h, w, int(H), int(W), out.data_ptr(), L.stream_ptr(z))
         return out
 
     def seg_tail_accum(self, z, zflip, geom, dst, H, W, accumulate=True, region=None):
@@ -1406,9 +1322,8 @@ class HipKernels:
                            int((ox + cols)[live].max())) if live.any() else (0, 0, 0, 0))
             g_dev = torch.from_numpy(g.astype(np.int32)).to(z.device)
         by0, by1, bx0, bx1 = (int(v) for v in region)
-        L.check(self.lib.tsg_seg_tail_accum(z.data_ptr(), L.ptr(zflip), dt, N, Cc, h, w, int(H), int(W), g_dev.data_ptr(),
-                                            dst.data_ptr(), Hd, Wd, by0, by1, bx0, bx1, int(bool(accumulate)),
-                                            L.stream_ptr(z)), "tsg_seg_tail_accum")
+        L.call(self.lib.tsg_seg_tail_accum, z.data_ptr(), L.ptr(zflip), dt, N, Cc, h, w, int(H), int(W), g_dev.data_ptr(),
+               dst.data_ptr(), Hd, Wd, by0, by1, bx0, bx1, int(bool(accumulate)), L.stream_ptr(z))
         return dst
 
     # ---- evaluation metric ----------------------------------------------------
@@ -1419,8 +1334,8 @@ class HipKernels:
             raise ValueError("pred and gt must have the same number of pixels")
         if out is None:
             out = torch.zeros(n_cl * n_cl + 3, dtype=torch.int64, device=gt.device)
-        L.check(self.lib.tsg_confusion_map(pred.data_ptr(), _label_code(pred), gt.data_ptr(), _label_code(gt),
-                                           gt.numel(), n_cl, out.data_ptr(), L.stream_ptr(gt)), "tsg_confusion_map")
+        L.call(self.lib.tsg_confusion_map, pred.data_ptr(), _label_code(pred), gt.data_ptr(), _label_code(gt), gt.numel(), n_cl,
+               out.data_ptr(), L.stream_ptr(gt))
         return out
 
     def confusion_logits(self, logits, gt, n_cl, out=None):
@@ -1432,8 +1347,8 @@ class HipKernels:
             raise ValueError("gt must have one label per pixel of logits")
         if out is None:
             out = torch.zeros(n_cl * n_cl + 3, dtype=torch.int64, device=gt.device)
-        L.check(self.lib.tsg_confusion_logits(logits.data_ptr(), L.dtype_code(logits), gt.data_ptr(), _label_code(gt),
-                                              B, Cc, HW, n_cl, out.data_ptr(), L.stream_ptr(gt)), "tsg_confusion_logits")
+        L.call(self.lib.tsg_confusion_logits, logits.data_ptr(), L.dtype_code(logits), gt.data_ptr(), _label_code(gt), B, Cc,
+               HW, n_cl, out.data_ptr(), L.stream_ptr(gt))
         return out
 
     SGD_MAX_SEGS = 128
@@ -1454,11 +1369,10 @@ class HipKernels:
     def sgd_multi_step_dev(self, ptrs, numel, group, lr_dev, momentum, weight_decay, blockmap, grad_scale=1.0):
         """ptrs: uint64 numpy [3, nseg] (param, grad, momentum buffer addresses); numel int64 / group int32 numpy
         [nseg]; momentum / weight_decay float32 numpy [ngroups]; blockmap from sgd_multi_blockmap."""
-        L.check(self.lib.tsg_sgd_multi_step_dev(ptrs[0].ctypes.data, ptrs[1].ctypes.data, ptrs[2].ctypes.data,
-                                                numel.ctypes.data, group.ctypes.data, len(numel), lr_dev.data_ptr(),
-                                                momentum.ctypes.data, weight_decay.ctypes.data, len(momentum),
-                                                blockmap.data_ptr(), blockmap.shape[0], float(grad_scale),
-                                                L.stream_ptr(lr_dev)), "tsg_sgd_multi_step_dev")
+        L.call(self.lib.tsg_sgd_multi_step_dev, ptrs[0].ctypes.data, ptrs[1].ctypes.data, ptrs[2].ctypes.data,
+               numel.ctypes.data, group.ctypes.data, len(numel), lr_dev.data_ptr(), momentum.ctypes.data,
+               weight_decay.ctypes.data, len(momentum), blockmap.data_ptr(), blockmap.shape[0], float(grad_scale),
+               L.stream_ptr(lr_dev))
 
     def multi_copy(self, srcs, dsts, blockmap=None, scale=1.0):
         """dsts[i].copy_(srcs[i]) * scale for lists of dense fp32 tensors with pairwise equal element order
@@ -1468,9 +1382,8 @@ class HipKernels:
         if blockmap is None:
             blockmap = self.sgd_multi_blockmap(numel, srcs[0].device)
         ptrs = np.array([[t.data_ptr() for t in srcs], [t.data_ptr() for t in dsts]], dtype=np.uint64)
-        L.check(self.lib.tsg_multi_copy_f32(ptrs[0].ctypes.data, ptrs[1].ctypes.data, numel.ctypes.data, len(srcs),
-                                            blockmap.data_ptr(), blockmap.shape[0], float(scale),
-                                            L.stream_ptr(srcs[0])), "tsg_multi_copy_f32")
+        L.call(self.lib.tsg_multi_copy_f32, ptrs[0].ctypes.data, ptrs[1].ctypes.data, numel.ctypes.data, len(srcs),
+               blockmap.data_ptr(), blockmap.shape[0], float(scale), L.stream_ptr(srcs[0]))
         return blockmap
 
 

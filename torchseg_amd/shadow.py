@@ -131,8 +131,8 @@ class _Bank(object):
         if not ents:
             return
         L = K.L
-        L.check(K.provider().lib.tsg_weight_shadow_refresh(table.data_ptr(), bmap.data_ptr(), bmap.shape[0],
-                                                           L.stream_ptr(table)), "tsg_weight_shadow_refresh")
+        L.call(K.provider().lib.tsg_weight_shadow_refresh, table.data_ptr(), bmap.data_ptr(), bmap.shape[0],
+               L.stream_ptr(table))
         for e in ents:
             p = e.ref()
             if p is not None:
@@ -166,8 +166,8 @@ class _Bank(object):
             return
         table, bmap, ents = t[0], t[1], t[2]
         L = K.L
-        L.check(K.provider().lib.tsg_weight_shadow_refresh(table.data_ptr(), bmap.data_ptr(), bmap.shape[0],
-                                                           L.stream_ptr(table)), "tsg_weight_shadow_refresh")
+        L.call(K.provider().lib.tsg_weight_shadow_refresh, table.data_ptr(), bmap.data_ptr(), bmap.shape[0],
+               L.stream_ptr(table))
         for e in ents:
             p = e.ref()
             if p is not None:
