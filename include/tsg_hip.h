@@ -412,7 +412,7 @@ int tsg_conv3x3_weight_rot180_t(const void* w, int dtype, void* out, int O, int 
  *   tsg_conv3x3_gen_tile: output channels per block (64 or 128) chosen for a problem size; the prepared filter is laid
  *     out for that width, so pass the same value (BN) to the preparation, the partial count and the forward call.
  *   tsg_conv3x3_gen_prep_filter: master weight w [O][3][3][I] (fp32 or bf16, the channels_last filter layout) ->
- *     out: tsg_conv3x3_gen_filter_elems() bf16 in MFMA fragment order (csrc/conv3g.hip).  mode 0: the forward filter
+ *     out: tsg_conv3x3_gen_filter_elems() bf16 in MFMA fragment order (csrc/tsg_mfma.h).  mode 0: the forward filter
  *     (the convolution then has C_out = O, C_in = I); mode 1: rot180 + transpose (C_out = I, C_in = O).
  *   tsg_conv3x3_gen_fwd: x [B,H,W,Cin] -> y [B,H,W,Cout], bf16 channels_last, fp32 accumulation.  partial (may be NULL):
  *     [S][2][Cout] fp32 sums / square sums of the bf16-rounded outputs, S = tsg_conv3x3_gen_stats_partials(...): the

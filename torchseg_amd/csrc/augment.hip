@@ -18,7 +18,7 @@
 //                 i0 >= in - 1 -> (in - 1, w = 0); the uint8 result is the interpolated value rounded to nearest.
 //   INTER_NEAREST: src = min(floor(dst * (in / out)), in - 1).
 // One thread per output pixel: 4 taps x 3 bytes in, 3 floats + 1 label out; no intermediate image ever exists.
-#include "tsg_common.h"
+#include "tsg_resample.h"
 
 namespace tsg {
 
@@ -44,15 +44,6 @@ struct AugBatch {
   int with_gt;
 };
 
-__device__ __forceinline__ void lin_index(int dst, double scale, int in, int& i0, int& i1, float& w) {
-  const double src = ((double)dst + 0.5) * scale - 0.5;        // cv2 computes this in double, then narrows the weight
-  int s = (int)floor(src);
-  float f = (float)(src - (double)s);
-  if (s < 0) { s = 0; f = 0.f; }
-  if (s >= in - 1) { s = in - 1; f = 0.f; }
-  i0 = s; i1 = s + 1 < in ? s + 1 : in - 1; w = f;
-}
-
 template <typename LT>
 __global__ __launch_bounds__(256) void augment_crop_k(AugBatch b, float* __restrict__ out_img, LT* __restrict__ out_gt) {
   const int sidx = blockIdx.z;
@@ -72,8 +63,8 @@ __global__ __launch_bounds__(256) void augment_crop_k(AugBatch b, float* __restr
   const int sy = p.crop_y + iy, sx = p.crop_x + ix;              // pixel of the (mirrored, scaled) image
   const double fy = p.fy, fx = p.fx;
   int y0, y1, x0, x1; float wy, wx;
-  lin_index(sy, fy, p.H, y0, y1, wy);
-  lin_index(sx, fx, p.W, x0, x1, wx);
+  hp_index(sy, fy, p.H, y0, y1, wy);
+  hp_index(sx, fx, p.W, x0, x1, wx);
   int ny = (int)floor((double)sy * fy); if (ny > p.H - 1) ny = p.H - 1;
   int nx = (int)floor((double)sx * fx); if (nx > p.W - 1) nx = p.W - 1;
   if (p.flip) { x0 = p.W - 1 - x0; x1 = p.W - 1 - x1; nx = p.W - 1 - nx; }   // resize(flip(img)) == flip-indexed taps

@@ -19,7 +19,6 @@
 //   bwd_reduce   2 reads           = 2s   (+s when the ReLU mask comes from y)
 //   bwd_apply    2 reads + 1 write = 3s   (+s mask-from-y, +s dres)
 #include "tsg_common.h"
-#include <stdlib.h>
 
 namespace tsg {
 
@@ -42,20 +41,6 @@ template <typename T> struct Pack<T, 1> {
   __device__ __forceinline__ void load(const T* p) { v[0] = ld1<T>(p); }
   __device__ __forceinline__ void store(T* p) const { st1<T>(p, v[0]); }
 };
-
-// V consecutive per-channel floats starting at c0 (c0 % V == 0 => 16-B aligned)
-template <int V>
-__device__ __forceinline__ void ldc(const float* __restrict__ p, int64_t c0, float (&o)[V]) {
-  if (V == 1) {
-    o[0] = p[c0];
-  } else {
-#pragma unroll
-    for (int q = 0; q < V / 4; ++q) {
-      const float4 t = *reinterpret_cast<const float4*>(p + c0 + 4 * q);
-      o[4 * q + 0] = t.x; o[4 * q + 1] = t.y; o[4 * q + 2] = t.z; o[4 * q + 3] = t.w;
-    }
-  }
-}
 
 struct NchwGeom {
   int seg;    // elements of one plane segment handled by one block-iteration
@@ -128,20 +113,6 @@ static int pick_vec(int dtype, int layout, int64_t C, int64_t HW, const void* p0
 template <typename T, int MODE> struct RedAcc { typedef float type; };
 template <> struct RedAcc<float, 0> { typedef double type; };
 template <> struct RedAcc<float, 1> { typedef double type; };
-
-// Block-wide sum of two doubles, fixed order; result valid in thread 0.  `sm` needs 2 * (blockDim.x / 64) doubles.
-__device__ __forceinline__ void block_sum2(double& a, double& b, double* sm) {
-  a = wave_sum(a);
-  b = wave_sum(b);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  if (lane == 0) { sm[2 * w] = a; sm[2 * w + 1] = b; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double ta = 0.0, tb = 0.0;
-    for (int i = 0; i < nw; ++i) { ta += sm[2 * i]; tb += sm[2 * i + 1]; }
-    a = ta; b = tb;
-  }
-}
 
 // one partial entry: fp32 accumulators store the value; fp64 accumulators store hi in row s and lo in row S + s (the
 // collapse / finalize kernels sum ALL rows in fp64, so the pair adds back to ~48 bits of the block's sum)
@@ -1121,7 +1092,6 @@ int tsg_bn_bwd_apply(const void* dy, const void* x, const void* y, void* dx, voi
   return V == 8 ? GO(bf16_t, 8) : GO(bf16_t, 1);
 #undef GO
 }
-
 
 // ---- ReLU mask as one bit per element (block tails: BN -> (+identity) -> ReLU) --------------------------------
 static int bits_vec(int dtype, int layout, int64_t C, int64_t HW, const void* a, const void* b, const void* c, const void* d,

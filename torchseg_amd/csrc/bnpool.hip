@@ -17,15 +17,6 @@ namespace tsg {
 
 constexpr int kBpT = 256;
 
-template <int V>
-__device__ __forceinline__ void bp_ldc(const float* __restrict__ p, int c0, float (&o)[V]) {
-#pragma unroll
-  for (int q = 0; q < V / 4; ++q) {
-    const float4 t = *reinterpret_cast<const float4*>(p + c0 + 4 * q);
-    o[4 * q + 0] = t.x; o[4 * q + 1] = t.y; o[4 * q + 2] = t.z; o[4 * q + 3] = t.w;
-  }
-}
-
 template <typename T> __device__ __forceinline__ float round_as(float v);
 template <> __device__ __forceinline__ float round_as<float>(float v) { return v; }
 template <> __device__ __forceinline__ float round_as<bf16_t>(float v) { return bf16_to_f32(f32_to_bf16(v)); }
@@ -99,8 +90,8 @@ __global__ __launch_bounds__(kBpT) void bn_relu_pool_fwd_k(const T* __restrict__
   const int oy1 = oy0 + kFwdRows < OH ? oy0 + kFwdRows : OH;
   const int64_t n = blockIdx.z;
   float a[V], b[V];
-  bp_ldc<V>(fp, g * V, a);
-  bp_ldc<V>(fp + C, g * V, b);
+  ldc<V>(fp, g * V, a);
+  ldc<V>(fp + C, g * V, b);
   const int x0 = 2 * ox - 1;
   const T* xn = x + n * IH * (int64_t)IW * C + g * V;
   float m0[V], m1[V], m2[V];
@@ -209,7 +200,7 @@ __global__ __launch_bounds__(kBpT) void bn_relu_pool_bwd_reduce_k(
 #pragma unroll
   for (int j = 0; j < V; ++j) { a1[j] = 0.f; a2[j] = 0.f; a[j] = 0.f; b[j] = 0.f; mu[j] = 0.f; }
   if (live) {
-    bp_ldc<V>(fp, g * V, a); bp_ldc<V>(fp + C, g * V, b); bp_ldc<V>(fp + 2 * C, g * V, mu);
+    ldc<V>(fp, g * V, a); ldc<V>(fp + C, g * V, b); ldc<V>(fp + 2 * C, g * V, mu);
     const T* xn = x + n * IH * (int64_t)IW * C + g * V;
     const T* dpn = dpool + n * OH * (int64_t)OW * C + g * V;
     const uint8_t* idn = idx + n * OH * (int64_t)OW * C + g * V;
@@ -278,11 +269,11 @@ __global__ __launch_bounds__(kBpT) void bn_relu_pool_bwd_apply_k(
   const int k1 = k0 + kAppRows < KH ? k0 + kAppRows : KH;
   const int64_t n = blockIdx.z;
   float a[V], b[V], mu[V], bc[V], c2[V];
-  bp_ldc<V>(bp, g * V, a);
-  bp_ldc<V>(bp + C, g * V, b);
-  bp_ldc<V>(bp + 2 * C, g * V, mu);
-  bp_ldc<V>(bp + 3 * C, g * V, bc);
-  bp_ldc<V>(bp + 4 * C, g * V, c2);
+  ldc<V>(bp, g * V, a);
+  ldc<V>(bp + C, g * V, b);
+  ldc<V>(bp + 2 * C, g * V, mu);
+  ldc<V>(bp + 3 * C, g * V, bc);
+  ldc<V>(bp + 4 * C, g * V, c2);
   const T* xn = x + n * IH * (int64_t)IW * C + g * V;
   T* dxn = dx + n * IH * (int64_t)IW * C + g * V;
   const T* dpn = dpool + n * OH * (int64_t)OW * C + g * V;

@@ -17,12 +17,9 @@
 //                                                                      B = x gathered; per-block partials folded in fp64 in a
 //                                                                      fixed order; dbias[n] = sum dz by a plane-sum kernel
 // All three are HBM-bound (x / dx once).  n_classes <= 32, C_in in {32, 64, 128, 256}, H*W a multiple of 16.
-#include "tsg_common.h"
+#include "tsg_mfma.h"
 
 namespace tsg {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 ch_bf16x8;
-typedef __attribute__((ext_vector_type(16))) float ch_f32x16;
 
 constexpr int CH_MAXN = 32;          // classes (one 32-row MFMA tile)
 constexpr int CH_MAXC = 256;
@@ -36,7 +33,7 @@ __global__ __launch_bounds__(256) void cls_fwd_k(const bf16_t* __restrict__ x, c
                                                  const float* __restrict__ bias, bf16_t* __restrict__ z, ChGeom g) {
   const int lane = threadIdx.x & 63, half = lane >> 5, l31 = lane & 31;
   // A fragment of k step ks: row (class) l31, k = 16 ks + 8 half .. + 7; classes >= N are zero rows
-  ch_bf16x8 af[KS];
+  bf16x8 af[KS];
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) {
     uint32_t pk[4] = {0u, 0u, 0u, 0u};
@@ -46,7 +43,7 @@ __global__ __launch_bounds__(256) void cls_fwd_k(const bf16_t* __restrict__ x, c
       pk[0] = pack2_bf16(a.x, a.y); pk[1] = pack2_bf16(a.z, a.w); pk[2] = pack2_bf16(b.x, b.y); pk[3] = pack2_bf16(b.z, b.w);
     }
     const uint4 v = make_uint4(pk[0], pk[1], pk[2], pk[3]);
-    af[ks] = __builtin_bit_cast(ch_bf16x8, v);
+    af[ks] = __builtin_bit_cast(bf16x8, v);
   }
   // bias of the 16 class rows this lane's accumulator registers hold: row = (r & 3) + 8 (r >> 2) + 4 half
   float bs[16];
@@ -64,12 +61,12 @@ __global__ __launch_bounds__(256) void cls_fwd_k(const bf16_t* __restrict__ x, c
     uint4 bv[KS];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) bv[ks] = *reinterpret_cast<const uint4*>(xr + ks * 16);
-    ch_f32x16 acc;
+    f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = bs[r];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks)
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ks], __builtin_bit_cast(ch_bf16x8, bv[ks]), acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ks], __builtin_bit_cast(bf16x8, bv[ks]), acc, 0, 0, 0);
     if (ok) {
       const int64_t b = p / g.HW, hw = p - b * g.HW;
       bf16_t* zb = z + b * g.N * g.HW + hw;
@@ -101,7 +98,7 @@ __global__ __launch_bounds__(256) void cls_dgrad_k(const bf16_t* __restrict__ dz
                                                    bf16_t* __restrict__ dx, ChGeom g) {
   const int lane = threadIdx.x & 63, half = lane >> 5, l31 = lane & 31;
   // B fragments: column c = 32 ct + l31, k = class 16 ks + 8 half + e (bf16-rounded master weight; classes >= N are zero)
-  ch_bf16x8 bw[CT][2];
+  bf16x8 bw[CT][2];
 #pragma unroll
   for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
@@ -113,7 +110,7 @@ __global__ __launch_bounds__(256) void cls_dgrad_k(const bf16_t* __restrict__ dz
         f[e] = n < g.N ? w[(int64_t)n * g.C + ct * 32 + l31] : 0.f;
       }
       const uint4 v = make_uint4(pack2_bf16(f[0], f[1]), pack2_bf16(f[2], f[3]), pack2_bf16(f[4], f[5]), pack2_bf16(f[6], f[7]));
-      bw[ct][ks] = __builtin_bit_cast(ch_bf16x8, v);
+      bw[ct][ks] = __builtin_bit_cast(bf16x8, v);
     }
   const int64_t ngroups = (g.P + 31) / 32;
   const int64_t wid = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nw = (int64_t)gridDim.x * 4;
@@ -124,7 +121,7 @@ __global__ __launch_bounds__(256) void cls_dgrad_k(const bf16_t* __restrict__ dz
     const bool ok = p < g.P;
     const int64_t pc = ok ? p : g.P - 1, b = pc / g.HW, hw = pc - b * g.HW;
     const bf16_t* zb = dz + b * g.N * g.HW + hw;
-    ch_bf16x8 az[2];
+    bf16x8 az[2];
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
       uint32_t h[8];
@@ -134,11 +131,11 @@ __global__ __launch_bounds__(256) void cls_dgrad_k(const bf16_t* __restrict__ dz
         h[e] = (ok && n < g.N) ? (uint32_t)zb[(int64_t)n * g.HW] : 0u;
       }
       const uint4 v = make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
-      az[ks] = __builtin_bit_cast(ch_bf16x8, v);
+      az[ks] = __builtin_bit_cast(bf16x8, v);
     }
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) {
-      ch_f32x16 acc;
+      f32x16 acc;
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[r] = 0.f;
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(az[0], bw[ct][0], acc, 0, 0, 0);
@@ -164,7 +161,7 @@ __global__ __launch_bounds__(256) void cls_wgrad_k(const bf16_t* __restrict__ dz
                                                    float* __restrict__ part, ChGeom g) {
   __shared__ float img[CT * 32 * 32];                                    // the block's sum, wave by wave (fixed order)
   const int lane = threadIdx.x & 63, half = lane >> 5, l31 = lane & 31, wave = threadIdx.x >> 6;
-  ch_f32x16 acc[CT];
+  f32x16 acc[CT];
 #pragma unroll
   for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
@@ -183,7 +180,7 @@ __global__ __launch_bounds__(256) void cls_wgrad_k(const bf16_t* __restrict__ dz
 #pragma unroll
       for (int e = 0; e < 8; ++e) h[e] = (uint32_t)xr[(int64_t)e * g.C + ct * 32];
       const uint4 bv = make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
-      acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(ch_bf16x8, av), __builtin_bit_cast(ch_bf16x8, bv), acc[ct], 0, 0, 0);
+      acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, av), __builtin_bit_cast(bf16x8, bv), acc[ct], 0, 0, 0);
     }
   }
   for (int wv = 0; wv < 4; ++wv) {

@@ -12,9 +12,9 @@
 //   * a block (8 waves, 2 per SIMD) owns 128 (or 64) output channels x an 8 x 32 pixel tile and walks the input channels
 //     in chunks of 16: per chunk the (8+2) x (32+2) x 16 input patch is staged ONCE and serves all nine taps from LDS
 //     (48-byte pixel stride: the 32 lanes of a ds_read_b128 fragment fall on distinct bank groups), and the 9 x BN x 16
-//     filter slab is a LINEAR copy: tsg_conv3x3_gen_prep_filter lays the filter out in MFMA fragment order
-//     [oc tile][chunk][tap][32-channel block][lane][8], so an A fragment is 1 KB of consecutive LDS (conflict-free by
-//     construction) — 166 staged bytes per MFMA against 512 for a 128 x 128 x 64 GEMM tile;
+//     filter slab is a LINEAR copy: tsg_conv3x3_gen_prep_filter lays the filter out in MFMA fragment order (the one
+//     definition of that order: frag_offset / frag_decode in tsg_mfma.h), so an A fragment is 1 KB of consecutive LDS
+//     (conflict-free by construction) — 166 staged bytes per MFMA against 512 for a 128 x 128 x 64 GEMM tile;
 //   * both LDS images are double-buffered: the global loads of chunk c+1 are issued before the 36 MFMAs per wave of
 //     chunk c and written behind them, one barrier per chunk;
 //   * a wave computes 64 oc x 2 rows x 32 pixels (4 accumulators); the 12 pixel fragments of a chunk (4 patch rows x 3
@@ -27,15 +27,10 @@
 //   * AFF: the input is relu(a x + b) of the tensor that is read (BatchNorm + ReLU in front of the convolution,
 //     resnet.py:36-46), applied while the patch is written to LDS with the values tsg_bn_apply_fwd would have stored.
 // x, y: NHWC bf16.  wf: the prepared filter.  fp32 accumulation, one rounding to bf16 at the store.
-#include "tsg_common.h"
-#include <stdlib.h>
+#include "tsg_mfma.h"
 #include <type_traits>
 
 namespace tsg {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 g3_bf16x8;
-typedef __attribute__((ext_vector_type(16))) float g3_f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned int g3_u32x4;
 
 constexpr int G3_TH = 8, G3_TW = 32;                     // output tile: 256 pixels
 constexpr int G3_PH = G3_TH + 2, G3_PW = G3_TW + 2;      // input patch
@@ -67,28 +62,6 @@ template <int BN, int NW> struct G3Cfg {
   static constexpr size_t LDS = (size_t)(2 * FELEMS + 2 * G3_PATCH) * 2 + 2 * G3_MAX_AFF_C * 4;
   static_assert(256 * OS <= 2 * FELEMS, "the output tile is staged in the two filter buffers");
 };
-
-// bf16(bf16 a + bf16 b) per element, fp32 add: what the eager `a + b` of two bf16 tensors computes
-__device__ __forceinline__ uint4 g3_add_bf16x8(uint4 a, uint4 b) {
-  const uint32_t x[4] = {a.x, a.y, a.z, a.w}, y[4] = {b.x, b.y, b.z, b.w};
-  uint32_t o[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    o[i] = pack2_bf16(__uint_as_float(x[i] << 16) + __uint_as_float(y[i] << 16),
-                      __uint_as_float(x[i] & 0xffff0000u) + __uint_as_float(y[i] & 0xffff0000u));
-  return make_uint4(o[0], o[1], o[2], o[3]);
-}
-
-__device__ __forceinline__ uint4 g3_affine_relu(uint4 v, const float* __restrict__ a, const float* __restrict__ b) {
-  uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float x0 = __uint_as_float(w[i] << 16), x1 = __uint_as_float(w[i] & 0xffff0000u);
-    const float y0 = fmaf(x0, a[2 * i], b[2 * i]), y1 = fmaf(x1, a[2 * i + 1], b[2 * i + 1]);
-    w[i] = pack2_bf16(y0 > 0.f ? y0 : 0.f, y1 > 0.f ? y1 : 0.f);
-  }
-  return make_uint4(w[0], w[1], w[2], w[3]);
-}
 
 // GLDS: the filter slab goes global -> LDS by LDS-DMA (global_load_lds_dwordx4: 1 KB per wave instruction, destination =
 // wave-uniform base + lane x 16 B — exactly the fragment-ordered slab, which is a linear copy), not through registers and
@@ -186,7 +159,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv3g_fwd_k(const bf16_t* __restr
             const int ih = oh0 - 1 + (prc[u] & 0xff), iw = ow0 - 1 + ((prc[u] >> 8) & 0xff);
             if (ih >= 0 && ih < g.H && iw >= 0 && iw < g.W) {     // padding pixels stay exactly zero
               const int c0 = chunk * G3_KC + part * 8;
-              v = g3_affine_relu(v, abs_ + c0, abs_ + g.Cin + c0);
+              v = affine_relu(v, abs_ + c0, abs_ + g.Cin + c0);
             }
           }
           const int pp = (prc[u] & 0xff) * G3_PW + ((prc[u] >> 8) & 0xff);
@@ -194,7 +167,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv3g_fwd_k(const bf16_t* __restr
         }
     };
 
-    g3_f32x16 acc[NOB][2];
+    f32x16 acc[NOB][2];
 #pragma unroll
     for (int j = 0; j < NOB; ++j)
 #pragma unroll
@@ -213,17 +186,17 @@ __global__ __launch_bounds__(64 * NW, 2) void conv3g_fwd_k(const bf16_t* __restr
       if (c + 1 < g.nchunks) fetch(c + 1, buf ^ 1);      // in flight during the MFMAs of this chunk
       const bf16_t* pb = pbuf + buf * G3_PATCH + ((2 * wp) * G3_PW + p) * G3_PS + half * 8;
       const bf16_t* fa = fbuf + buf * Cfg::FELEMS + ((wo * NOB) * 64 + lane) * 8;
-      g3_bf16x8 bq[4][3];
+      bf16x8 bq[4][3];
 #pragma unroll
       for (int pr = 0; pr < 4; ++pr)
 #pragma unroll
         for (int kw = 0; kw < 3; ++kw)
-          bq[pr][kw] = *reinterpret_cast<const g3_bf16x8*>(pb + (pr * G3_PW + kw) * G3_PS);
+          bq[pr][kw] = *reinterpret_cast<const bf16x8*>(pb + (pr * G3_PW + kw) * G3_PS);
       // the filter fragments of tap t + 1 are read while the MFMAs of tap t run (two register sets; with one, every tap
       // began with an exposed LDS latency: ds_read, s_waitcnt lgkmcnt(0), 4 MFMAs in the ISA)
-      g3_bf16x8 af[2][NOB];
+      bf16x8 af[2][NOB];
 #pragma unroll
-      for (int j = 0; j < NOB; ++j) af[0][j] = *reinterpret_cast<const g3_bf16x8*>(fa + (j * 64) * 8);
+      for (int j = 0; j < NOB; ++j) af[0][j] = *reinterpret_cast<const bf16x8*>(fa + (j * 64) * 8);
       // (the scheduler otherwise sinks every read to just before its first use, to save registers this kernel has to spare)
       __builtin_amdgcn_sched_barrier(0);
       // two independent blocks share a CU: the one inside its MFMA cluster outranks the one that is staging (guide T5:
@@ -235,7 +208,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv3g_fwd_k(const bf16_t* __restr
         if (t + 1 < 9) {
 #pragma unroll
           for (int j = 0; j < NOB; ++j)
-            af[(t + 1) & 1][j] = *reinterpret_cast<const g3_bf16x8*>(fa + (((t + 1) * OCB + j) * 64) * 8);
+            af[(t + 1) & 1][j] = *reinterpret_cast<const bf16x8*>(fa + (((t + 1) * OCB + j) * 64) * 8);
           __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
@@ -274,7 +247,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv3g_fwd_k(const bf16_t* __restr
         const int64_t off = ((int64_t)oh * g.W + ow) * g.Cout + part * 8;
         // addend: y = bf16(bf16(conv) + addend) — the gradient that reaches the same tensor through a skip connection
         // (resnet.py:48-52: out += residual), summed here instead of by a separate pass over three tensors
-        if (addend) o = g3_add_bf16x8(o, *reinterpret_cast<const uint4*>(addend + img_off + off));
+        if (addend) o = add_bf16x8(o, *reinterpret_cast<const uint4*>(addend + img_off + off));
         *reinterpret_cast<uint4*>(yimg + off) = o;
         if (STATS) {                                     // the values just stored: no second pass over the tile
           const uint32_t w[4] = {o.x, o.y, o.z, o.w};
@@ -355,7 +328,7 @@ __global__ __launch_bounds__(256, 2) void conv3h_fwd_k(const bf16_t* __restrict_
   bf16_t* outs = reinterpret_cast<bf16_t*>(h3_smem);
   float* red = reinterpret_cast<float*>(h3_smem + H3_RED);
 
-  // the block's filter slabs [chunk][tap][ocb][lane][8] as one buffer; piece q of chunk c at byte (c 18 + q) 1024
+  // the block's filter slabs [chunk][tap][ocb][lane][8] (tsg_mfma.h) as one buffer; piece q of chunk c at byte (c 18 + q) 1024
   const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
       (void*)(wf + (int64_t)oct * g.nchunks * (H3_FBYTES / 2)), 0, g.nchunks * H3_FBYTES, 0x00020000);
   const unsigned char* fa = h3_smem + lane * 16;                                           // A fragment (tap, ocb) at + (tap 2 + ocb) 1024
@@ -388,7 +361,7 @@ __global__ __launch_bounds__(256, 2) void conv3h_fwd_k(const bf16_t* __restrict_
                                                  (chunk * H3_FPIECES + q) * 1024, 0, 0);
     };
 
-    g3_f32x16 acc[2][4];
+    f32x16 acc[2][4];
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -413,11 +386,11 @@ __global__ __launch_bounds__(256, 2) void conv3h_fwd_k(const bf16_t* __restrict_
       const bool more = c + 1 < g.nchunks;
       const unsigned char* fab = fa + buf * H3_FBYTES;
       const unsigned char* pbb = pb + buf * H3_PBYTES;
-      g3_bf16x8 bq[2][6], af[2][2];
+      bf16x8 bq[2][6], af[2][2];
 #pragma unroll
-      for (int r = 0; r < 6; ++r) bq[0][r] = *reinterpret_cast<const g3_bf16x8*>(pbb + (r * G3_PW) * 32);
+      for (int r = 0; r < 6; ++r) bq[0][r] = *reinterpret_cast<const bf16x8*>(pbb + (r * G3_PW) * 32);
 #pragma unroll
-      for (int j = 0; j < 2; ++j) af[0][j] = *reinterpret_cast<const g3_bf16x8*>(fab + j * 1024);
+      for (int j = 0; j < 2; ++j) af[0][j] = *reinterpret_cast<const bf16x8*>(fab + j * 1024);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int s = 0; s < 9; ++s) {                      // MFMA group s: column shift kw = s / 3, kernel row kh = s % 3
@@ -425,12 +398,12 @@ __global__ __launch_bounds__(256, 2) void conv3h_fwd_k(const bf16_t* __restrict_
         if (s + 1 < 9) {
           const int t1 = ((s + 1) % 3) * 3 + (s + 1) / 3;
 #pragma unroll
-          for (int j = 0; j < 2; ++j) af[(s + 1) & 1][j] = *reinterpret_cast<const g3_bf16x8*>(fab + (t1 * 2 + j) * 1024);
+          for (int j = 0; j < 2; ++j) af[(s + 1) & 1][j] = *reinterpret_cast<const bf16x8*>(fab + (t1 * 2 + j) * 1024);
         }
         if (kw + 1 < 3) {
 #pragma unroll
           for (int e = 0; e < 2; ++e)
-            bq[(kw + 1) & 1][2 * kh + e] = *reinterpret_cast<const g3_bf16x8*>(pbb + ((2 * kh + e) * G3_PW + kw + 1) * 32);
+            bq[(kw + 1) & 1][2 * kh + e] = *reinterpret_cast<const bf16x8*>(pbb + ((2 * kh + e) * G3_PW + kw + 1) * 32);
         }
         if (more) {                                      // chunk c + 1: the patch (HBM / L2) first, the filter (L2) behind it
           if (s == 0) { dma_patch(0, c + 1, buf ^ 1); dma_patch(1, c + 1, buf ^ 1); }
@@ -482,7 +455,7 @@ __global__ __launch_bounds__(256, 2) void conv3h_fwd_k(const bf16_t* __restrict_
         (void*)(addend + (int64_t)bimg * g.H * g.W * g.Cout), 0, g.H * g.W * g.Cout * 2, 0x00020000);
     const int av0 = ow < g.W ? (oh0 * g.W + ow) * g.Cout * 2 + oct * 128 + part * 16 : (int)0x80000000;
     const int arow = g.W * g.Cout * 2;
-    g3_u32x4 adc[4], adn[4];
+    u32x4 adc[4], adn[4];
     __builtin_amdgcn_sched_barrier(0);                   // (after the staging stores: the accumulators' registers are free)
     if (has_add) {
 #pragma unroll
@@ -503,7 +476,7 @@ __global__ __launch_bounds__(256, 2) void conv3h_fwd_k(const bf16_t* __restrict_
         for (int e = 0; e < 4; ++e) {
           if (k4 + e < rows) {
             uint4 o = *reinterpret_cast<const uint4*>(op + 32 * (k4 + e) * H3_OS);
-            if (has_add) o = g3_add_bf16x8(o, make_uint4(adc[e][0], adc[e][1], adc[e][2], adc[e][3]));
+            if (has_add) o = add_bf16x8(o, make_uint4(adc[e][0], adc[e][1], adc[e][2], adc[e][3]));
             *reinterpret_cast<uint4*>(yp) = o;
           }
           yp += (int64_t)g.W * g.Cout;
@@ -521,25 +494,23 @@ __global__ __launch_bounds__(256, 2) void conv3h_fwd_k(const bf16_t* __restrict_
       // 32 MFMAs + 32 LDS reads per wave and tile instead of unpack / add / fma per element and 48 cross-lane shuffles, and
       // no statistics registers live across the K loop; time-neutral at the bench shapes (+3 ... +9 us per launch for the
       // statistics either way, profiles/r04_conv3h.txt).
-      typedef short h3_v4i16 __attribute__((ext_vector_type(4)));
-      typedef h3_v4i16 __attribute__((address_space(3))) h3_lds_v4i16;
       const int sub = (lane >> 4) & 1, i16 = lane & 15;
       const bf16_t* fr = outs + (128 * wave + 8 * half + (i16 >> 2)) * H3_OS + 16 * sub + 4 * (i16 & 3);
-      g3_f32x16 d1[2], d2[2];
+      f32x16 d1[2], d2[2];
 #pragma unroll
       for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
         for (int r = 0; r < 16; ++r) { d1[cb][r] = 0.f; d2[cb][r] = 0.f; }
-      union { uint32_t u[4]; g3_bf16x8 v; } ones;
+      union { uint32_t u[4]; bf16x8 v; } ones;
 #pragma unroll
       for (int e = 0; e < 4; ++e) ones.u[e] = 0x3f803f80u;
 #pragma unroll
       for (int ks = 0; ks < 8; ++ks)
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb) {
-          union { h3_v4i16 q[2]; g3_bf16x8 v; } f;
-          f.q[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((h3_lds_v4i16*)(fr + (ks * 16 + 0) * H3_OS + cb * 32));
-          f.q[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((h3_lds_v4i16*)(fr + (ks * 16 + 4) * H3_OS + cb * 32));
+          union { v4i16 q[2]; bf16x8 v; } f;
+          f.q[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16*)(fr + (ks * 16 + 0) * H3_OS + cb * 32));
+          f.q[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16*)(fr + (ks * 16 + 4) * H3_OS + cb * 32));
           d1[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones.v, f.v, d1[cb], 0, 0, 0);
           d2[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.v, f.v, d2[cb], 0, 0, 0);
         }
@@ -585,7 +556,7 @@ __global__ __launch_bounds__(256, 2) void conv3h_fwd_k(const bf16_t* __restrict_
 // dy rows = 4 parities x 2 rows = 8 accumulators; K = the convolution's output channels in chunks of 32 (two MFMA K
 // steps per barrier: 36 MFMAs per wave).  Staging as in conv3h_fwd_k: everything by LDS-DMA, the (8+1) x (32+1) dy patch
 // as two 16-channel planes of 32-byte pixels, out-of-image pixels by out-of-range buffer offsets; the filter is the
-// mode-1 prepared filter at tile width 32 ([ci tile][chunk][tap'][lane][8] with tap' = 8 - (3 kh + kw)).  `addend`
+// mode-1 prepared filter at tile width 32 (tsg_mfma.h: [ci tile][chunk][tap'][lane][8], tap' = 8 - (3 kh + kw)).  `addend`
 // (the gradient that reaches x through the shortcut branch, resnet.py:48-52) joins in the epilogue.
 constexpr int D2_TH = 8, D2_PR = D2_TH + 1, D2_PC = G3_TW + 1;      // dy tile rows, patch rows / columns
 constexpr int D2_NPX = D2_PR * D2_PC;                    // 297 patch pixels
@@ -645,7 +616,7 @@ __global__ __launch_bounds__(256, 2) void conv3s2d_k(const bf16_t* __restrict__ 
                                                  lane * 16, (chunk * D2_FPIECES + q) * 1024, 0, 0);
     };
 
-    g3_f32x16 acc[4][2];                                  // [2 pa + pb][dy row of the wave]
+    f32x16 acc[4][2];                                  // [2 pa + pb][dy row of the wave]
 #pragma unroll
     for (int c = 0; c < 4; ++c)
 #pragma unroll
@@ -665,14 +636,14 @@ __global__ __launch_bounds__(256, 2) void conv3s2d_k(const bf16_t* __restrict__ 
       const unsigned char* pbb = pb + buf * (D2_FBYTES + D2_PBYTES);
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        g3_bf16x8 bq[3][2], af[9];
+        bf16x8 bq[3][2], af[9];
 #pragma unroll
         for (int r = 0; r < 3; ++r)
 #pragma unroll
           for (int dc = 0; dc < 2; ++dc)
-            bq[r][dc] = *reinterpret_cast<const g3_bf16x8*>(pbb + ks * (D2_PVEC * 16) + (r * D2_PC + dc) * 32);
+            bq[r][dc] = *reinterpret_cast<const bf16x8*>(pbb + ks * (D2_PVEC * 16) + (r * D2_PC + dc) * 32);
 #pragma unroll
-        for (int t = 0; t < 9; ++t) af[t] = *reinterpret_cast<const g3_bf16x8*>(fab + (ks * 9 + (8 - t)) * 1024);
+        for (int t = 0; t < 9; ++t) af[t] = *reinterpret_cast<const bf16x8*>(fab + (ks * 9 + (8 - t)) * 1024);
         if (more) {
           if (ks == 0) { dma(0, c + 1, buf ^ 1); dma(1, c + 1, buf ^ 1); dma(2, c + 1, buf ^ 1); }
           else { dma(3, c + 1, buf ^ 1); dma(4, c + 1, buf ^ 1); }
@@ -725,7 +696,7 @@ __global__ __launch_bounds__(256, 2) void conv3s2d_k(const bf16_t* __restrict__ 
       return sub ? __builtin_amdgcn_raw_buffer_load_b128(ra, (k & 1) ? (int)0x80000000 : av0, (k >> 1) * arow, 0)
                  : __builtin_amdgcn_raw_buffer_load_b128(ra, av0, k * arow, 0);
     };
-    g3_u32x4 adc[4], adn[4];
+    u32x4 adc[4], adn[4];
     __builtin_amdgcn_sched_barrier(0);                   // (after the staging stores: the accumulators' registers are free)
     if (has_add) {
 #pragma unroll
@@ -749,7 +720,7 @@ __global__ __launch_bounds__(256, 2) void conv3s2d_k(const bf16_t* __restrict__ 
             const uint2 lo = *reinterpret_cast<const uint2*>(op + 64 * (k4 + e) * D2_OS);
             const uint2 hi = *reinterpret_cast<const uint2*>(op + 64 * (k4 + e) * D2_OS + 4);
             uint4 o = make_uint4(lo.x, lo.y, hi.x, hi.y);
-            if (has_add) o = g3_add_bf16x8(o, make_uint4(adc[e][0], adc[e][1], adc[e][2], adc[e][3]));
+            if (has_add) o = add_bf16x8(o, make_uint4(adc[e][0], adc[e][1], adc[e][2], adc[e][3]));
             *reinterpret_cast<uint4*>(xp) = o;
           }
           xp += (int64_t)XW * g.Cout;
@@ -761,8 +732,8 @@ __global__ __launch_bounds__(256, 2) void conv3s2d_k(const bf16_t* __restrict__ 
   }
 }
 
-// ---- filter preparation: fp32 / bf16 master weight [O][3][3][I] (channels_last filter) -> bf16 in fragment order
-//   out[oc tile][chunk][tap][ocb][lane][e] = W'[oc = tile BN + ocb 32 + (lane & 31)][tap][ci = chunk 16 + (lane >> 5) 8 + e]
+// ---- filter preparation: fp32 / bf16 master weight [O][3][3][I] (channels_last filter) -> bf16 W' in fragment order
+// (tsg_mfma.h: frag_offset / frag_decode), one 16-byte vector per thread.
 // mode 0: W' = w (forward: C_out' = O, C_in' = I).
 // mode 1: W'[oc'][tap][ci'] = w[ci'][8 - tap][oc'] (data gradient: C_out' = I, C_in' = O).
 template <typename TI>
@@ -771,6 +742,8 @@ __global__ __launch_bounds__(256) void g3_prep_filter_k(const TI* __restrict__ w
   const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (v >= nvec) return;
   const int Co = mode ? I : O, Ci = mode ? O : I;        // of the convolution that will run
+  // frag_decode(v, nch, ocb_n) of tsg_mfma.h, spelt out: through the shared function this 64-bit form compiles to other
+  // code than it always has (the weight-shadow refresh, which decodes in 32 bits, calls it)
   const int nch = Ci / G3_KC, ocb_n = BN / 32;
   int64_t r = v;
   const int ln = (int)(r % 64); r /= 64;
@@ -801,23 +774,19 @@ __global__ __launch_bounds__(256) void g3_prep_filter_k(const TI* __restrict__ w
 static int g3_bn(int64_t B, int64_t H, int64_t W, int Cout) {
   (void)B; (void)H; (void)W;
   if (Cout % 128) return 64;
-  if (const char* e = getenv("TSG_CONV3G_BN")) {
-    const int v = atoi(e);
-    if (v == 64 || v == 128) return v;
-  }
-  return 64;
+  return tsg_env_int("TSG_CONV3G_BN", 64) == 128 ? 128 : 64;            // read on every call
 }
 
 // TSG_CONV3G_GLDS=1|0 (default 1): filter slab by LDS-DMA.  profiles/r03_conv3g_glds.log: per step of forwards 1258 vs
 // 1320 us, data gradients 1211 vs 1220 us, the bench 1125.3 vs 1123.3 img/s in two interleaved pairs — small, repeatable
 static bool g3_glds() {
-  static const int v = [] { const char* e = getenv("TSG_CONV3G_GLDS"); return e ? atoi(e) : 1; }();
+  static const int v = tsg_env_int("TSG_CONV3G_GLDS", 1);
   return v != 0;
 }
 
 // waves per block: 4 (two blocks per CU) for 64-wide tiles unless TSG_CONV3G_NW=8
 static int g3_nw(int BN) {
-  static const int forced = [] { const char* e = getenv("TSG_CONV3G_NW"); return e ? atoi(e) : 0; }();
+  static const int forced = tsg_env_int("TSG_CONV3G_NW", 0);
   if (BN == 128) return 8;
   return forced == 8 ? 8 : 4;
 }
@@ -833,13 +802,13 @@ static int g3_geom(G3Geom* g, int64_t B, int64_t H, int64_t W, int Cin, int Cout
   // one 8-wave block (~110 KB of LDS) or two 4-wave blocks (~74 KB each) per CU: ~256 / ~512 blocks in all, a multiple
   // of 8 slots per oc tile (XCD mapping)
   static int target = 0;
-  if (!target) { const char* e = getenv("TSG_CONV3G_BLOCKS"); target = e ? atoi(e) : 256; if (target < 8) target = 256; }
+  if (!target) { target = tsg_env_int("TSG_CONV3G_BLOCKS", 256); if (target < 8) target = 256; }
   int64_t ns = (g3_nw(BN) == 4 ? 2 * target : target) / g->noct;
   if (ns > g->ntiles) ns = g->ntiles;
   ns = (ns + 7) / 8 * 8;
   if (ns < 8) ns = 8;
   g->nslots = (int)ns;
-  static const int prio = [] { const char* e = getenv("TSG_MFMA_PRIO"); return e ? atoi(e) : 0; }();
+  static const int prio = tsg_env_int("TSG_MFMA_PRIO", 0);
   g->prio = prio;
   return 0;
 }
@@ -850,8 +819,7 @@ static int g3_geom(G3Geom* g, int64_t B, int64_t H, int64_t W, int Cin, int Cout
 // equals conv3g_fwd_k's for the same problem, so the statistics partial has the same rows whichever kernel runs.
 // TSG_CONV3G_V2=0 keeps every problem on conv3g_fwd_k, =2 sends every problem it can run to conv3h_fwd_k (tests).
 static bool g3_v2_geom(G3Geom* g, int BN) {
-  const char* e = getenv("TSG_CONV3G_V2");               // 0: never, 1 (default): where it fills the grid, 2: wherever it can run
-  const int on = e ? atoi(e) : 1;
+  const int on = tsg_env_int("TSG_CONV3G_V2", 1);        // 0: never, 1 (default): where it fills the grid, 2: wherever it can run
   if (!on || BN != 64 || g3_nw(64) != 4 || (g->nchunks & 1)) return false;
   const int64_t th = (g->H + H3_TH - 1) / H3_TH;
   const int64_t nt = (int64_t)g->B * th * g->tiles_w;

@@ -13,18 +13,9 @@
 //        121 dwords spreads the 32 lanes of a ds_read_b32 over the 32 banks.
 // A block's 4 waves own the whole [64 x 576] accumulator (9 tiles of 32x32 each: oc half x ci half x 9 taps)
 // in MFMA registers across all its tiles; per-block partials are summed in fp64 in a fixed order.
-#include "tsg_common.h"
-#include <stdlib.h>
+#include "tsg_mfma.h"
 
 namespace tsg {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-// The LDS images are written with 16- and 32-bit stores and read back as 32- and 128-bit fragments: every
-// access goes through may_alias types so that type-based alias analysis cannot reorder or drop them.
-typedef uint32_t __attribute__((may_alias)) lds_u32;
-typedef uint16_t __attribute__((may_alias)) lds_u16;
-typedef bf16x8 __attribute__((may_alias)) lds_bf16x8;
 
 constexpr int W3_C = 64;                    // channels in and out
 constexpr int W3_N = 9 * W3_C;              // 576 = (tap, ci)
@@ -163,8 +154,6 @@ __global__ __launch_bounds__(256) void conv3_wrw_k(const bf16_t* __restrict__ x,
 // S[i][0..3]; lane l receives S[4 j + (l >> 2)][l & 3], j = 0..3.  Pointing source lane 4 j + r at
 // (pixel k0 + j, channels c0 + 4 r ..) therefore hands lane 4 r + c the channel c0 + 4 r + c at pixels k0 .. k0 + 3:
 // two reads make one MFMA fragment, and a tap shift is a pixel offset (no alignment copies).
-typedef short v4i16 __attribute__((ext_vector_type(4)));
-typedef v4i16 __attribute__((address_space(3))) lds_v4i16;
 
 constexpr int T3_RBE = 96;                          // bf16 elements per pixel row in LDS: 64 channels + 32 pad (192 B:
                                                     // two 16-lane groups of a transposing read hit 64 distinct banks)
@@ -177,20 +166,7 @@ constexpr size_t T3_LDS = (size_t)(T3_DY + T3_NPX * T3_RBE) * sizeof(bf16_t);   
 // Normalise-on-load (AFF): x is the input of a BatchNorm + ReLU whose output the convolution consumed (csrc/conv64.hip):
 // the x patch is transformed to relu(a x + b) — with tsg_bn_apply_fwd's arithmetic and rounding — while it is staged, so
 // the weight gradient sees the activation the forward convolution saw without that activation ever being stored.
-__device__ __forceinline__ uint4 w3_affine_relu(uint4 v, const float* __restrict__ ab, int part8) {
-  uint32_t w[4] = {v.x, v.y, v.z, v.w};
-  const float4 a0 = *reinterpret_cast<const float4*>(ab + part8), a1 = *reinterpret_cast<const float4*>(ab + part8 + 4);
-  const float4 b0 = *reinterpret_cast<const float4*>(ab + W3_C + part8), b1 = *reinterpret_cast<const float4*>(ab + W3_C + part8 + 4);
-  const float a[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-  const float b[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float x0 = __uint_as_float(w[i] << 16), x1 = __uint_as_float(w[i] & 0xffff0000u);
-    const float y0 = fmaf(x0, a[2 * i], b[2 * i]), y1 = fmaf(x1, a[2 * i + 1], b[2 * i + 1]);
-    w[i] = pack2_bf16(y0 > 0.f ? y0 : 0.f, y1 > 0.f ? y1 : 0.f);
-  }
-  return make_uint4(w[0], w[1], w[2], w[3]);
-}
+// affine_relu(v, ab, W3_C, part8) of tsg_mfma.h.
 
 template <bool AFF>
 __global__ __launch_bounds__(256) void conv3_wrw_tr_k(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dy,
@@ -259,7 +235,7 @@ __global__ __launch_bounds__(256) void conv3_wrw_tr_k(const bf16_t* __restrict__
         uint4 v = rx[u];
         if (AFF) {
           const int ih = cur_oh0 - 1 + xr[u], iw = cur_ow0 - 1 + xc[u];
-          if (ih >= 0 && ih < g.H && iw >= 0 && iw < g.W) v = w3_affine_relu(v, abs_, spart * 8);
+          if (ih >= 0 && ih < g.H && iw >= 0 && iw < g.W) v = affine_relu(v, abs_, W3_C, spart * 8);
         }
         *reinterpret_cast<uint4*>(xL + (spix + 32 * u) * T3_RBE + spart * 8) = v;
       }
@@ -461,7 +437,7 @@ __global__ __launch_bounds__(256, PF ? 1 : 2) void conv3_wrw_gen_k(const bf16_t*
         uint4 v = qx_[u];
         const int ih = S * cur_oh0 - 1 + xr[u], iw = S * cur_ow0 - 1 + xc[u];
         const bool in = ih >= 0 && ih < g.Hin && iw >= 0 && iw < g.Win;
-        if (AFF && in) v = w3_affine_relu(v, abs_, spart * 8);
+        if (AFF && in) v = affine_relu(v, abs_, W3_C, spart * 8);
         if (rezero && !in) v = make_uint4(0, 0, 0, 0);
         *reinterpret_cast<uint4*>(xL + (spix + 32 * u) * T3_RBE + spart * 8) = v;
       }
@@ -763,11 +739,11 @@ int tsg_conv3x3_wrw_tr_norm(const void* x, const float* in_ab, const void* dy, f
 // (profiles/r03_conv3wrw_two_tiles_ahead.txt: 2.76 vs 2.37 ms per step, 1100 vs 1125 img/s on one box; layer3 at the same
 // occupancy 123 vs 105 us): the tile time is not the load latency the 2.1 us per tile suggested
 static bool w3_pf2() {
-  static const bool v = [] { const char* e = getenv("TSG_CONV_WRW_PF2"); return e && e[0] == '1'; }();
+  static const bool v = tsg_env_flag("TSG_CONV_WRW_PF2", false);
   return v;
 }
 static bool w3_occ2(int64_t ntiles) {
-  static const int v = [] { const char* e = getenv("TSG_CONV_WRW_OCC"); return e ? atoi(e) : 1; }();
+  static const int v = tsg_env_int("TSG_CONV_WRW_OCC", 1);
   return !w3_pf2() && v == 2 && ntiles >= 1024;
 }
 
@@ -783,16 +759,16 @@ static int w3gen_geom(W3GenGeom* g, int64_t B, int64_t Hin, int64_t Win, int Cin
   // one block per CU at a time (300 registers per lane): a second round of blocks would only add partials to fold
   // (measured: 256 blocks 826 img/s, 512 blocks 815, 128 blocks 789)
   static int target = 0;
-  if (!target) { const char* e = getenv("TSG_CONV_WRW_BLOCKS"); target = e ? atoi(e) : 256; if (target < 1) target = 256; }
+  if (!target) { target = tsg_env_int("TSG_CONV_WRW_BLOCKS", 256); if (target < 1) target = 256; }
   int bpp = ((stride == 1 && w3_occ2(g->ntiles) ? 2 * target : target) + g->npairs - 1) / g->npairs;
   if (bpp > g->ntiles) bpp = g->ntiles;
   if (bpp < 1) bpp = 1;
   // slots per pair: a multiple of 8 (one XCD per slot residue), or of 4 with a slot's pairs on two XCDs when 8 slots
   // would be more blocks than CUs (TSG_CONV_WRW_XS2=0 restores the round-3 mapping)
-  static const bool xs2 = [] { const char* e = getenv("TSG_CONV_WRW_XS2"); return !(e && e[0] == '0'); }();
+  static const bool xs2 = tsg_env_flag("TSG_CONV_WRW_XS2", true);
   g->xs = (xs2 && bpp <= 4 && g->npairs % 2 == 0 && g->npairs * 8 > target) ? 2 : 1;
   g->bpp = g->xs == 2 ? (bpp + 3) / 4 * 4 : (bpp + 7) / 8 * 8;
-  static const int prio = [] { const char* e = getenv("TSG_MFMA_PRIO"); return e ? atoi(e) : 0; }();
+  static const int prio = tsg_env_int("TSG_MFMA_PRIO", 0);
   g->prio = prio;
   return 0;
 }
@@ -821,7 +797,7 @@ static int conv3_wrw_gen_common(const void* x, const float* in_ab, const void* d
   hipStream_t st = (hipStream_t)stream;
   // raw buffer loads in the fetch (see the kernel's comment) unless TSG_CONV_WRW_BUF=0 or a thread's offsets inside a
   // tile could reach the 2 GB the descriptor covers (the base is per tile, so this takes a row of > 10^8 elements)
-  static const bool buf_env = [] { const char* e = getenv("TSG_CONV_WRW_BUF"); return !(e && e[0] == '0'); }();
+  static const bool buf_env = tsg_env_flag("TSG_CONV_WRW_BUF", true);
   const bool buf = buf_env && (int64_t)(3 * stride + 4) * Win * Cin * 2 < 0x40000000LL && (int64_t)5 * g.W * Cout * 2 < 0x40000000LL;
 #define W3_GO2(SS, PFF, AF, BF)                                                                                   \
   do {                                                                                                            \
@@ -841,7 +817,7 @@ static int conv3_wrw_gen_common(const void* x, const float* in_ab, const void* d
 #undef W3_GO2
   TSG_CHECK_LAUNCH();
   // TSG_CONV_WRW_FOLD=2 (default) | 1: conv3_wrw_gen_fold2 (row lanes sized to the slot count) | the round-2 fold
-  static const bool fold2 = [] { const char* e = getenv("TSG_CONV_WRW_FOLD"); return !(e && e[0] == '1'); }();
+  static const bool fold2 = !tsg_env_flag("TSG_CONV_WRW_FOLD", false);
   if (fold2) {
     const int T = g.bpp <= 8 ? 1 : g.bpp <= 16 ? 2 : g.bpp <= 32 ? 4 : g.bpp <= 64 ? 8 : 16;
     const int64_t blocks = (int64_t)g.npairs * (W3_C * W3_N / 4) / (256 / T);

@@ -17,13 +17,9 @@
 //   * STATS: per-channel sum / square sum of the bf16-rounded outputs in the epilogue (the statistics pass of the
 //     BatchNorm that follows every one of these convolutions), partial[block][2][64].
 // x, y: NHWC bf16.  w: bf16 [oc][kh][kw][ci] (the channels_last filter layout).
-#include "tsg_common.h"
-#include <stdlib.h>
+#include "tsg_mfma.h"
 
 namespace tsg {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 c6_bf16x8;
-typedef __attribute__((ext_vector_type(16))) float c6_f32x16;
 
 constexpr int C6_C = 64;
 constexpr int C6_TH = 4, C6_TW = 32;                     // output tile
@@ -72,31 +68,7 @@ __device__ __forceinline__ void c6_fetch(const bf16_t* __restrict__ x, const C6G
 // that precedes these convolutions in the spatial path and inside a BasicBlock (seg_oprs.py:39-46, resnet.py:36-46) —
 // applied while the patch is written to LDS, with the values tsg_bn_apply_fwd would have stored (same fma, same
 // rounding to bf16), so the normalised activation is never written or re-read.  Padding pixels stay exactly zero.
-__device__ __forceinline__ uint4 c6_affine_relu(uint4 v, const float* __restrict__ ab, int part8) {
-  uint32_t w[4] = {v.x, v.y, v.z, v.w};
-  const float4 a0 = *reinterpret_cast<const float4*>(ab + part8), a1 = *reinterpret_cast<const float4*>(ab + part8 + 4);
-  const float4 b0 = *reinterpret_cast<const float4*>(ab + C6_C + part8), b1 = *reinterpret_cast<const float4*>(ab + C6_C + part8 + 4);
-  const float a[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-  const float b[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float x0 = __uint_as_float(w[i] << 16), x1 = __uint_as_float(w[i] & 0xffff0000u);
-    const float y0 = fmaf(x0, a[2 * i], b[2 * i]), y1 = fmaf(x1, a[2 * i + 1], b[2 * i + 1]);
-    w[i] = pack2_bf16(y0 > 0.f ? y0 : 0.f, y1 > 0.f ? y1 : 0.f);
-  }
-  return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-// bf16(bf16 a + bf16 b) per element, fp32 add: what the eager `a + b` of two bf16 tensors computes
-__device__ __forceinline__ uint4 c6_add_bf16x8(uint4 a, uint4 b) {
-  const uint32_t x[4] = {a.x, a.y, a.z, a.w}, y[4] = {b.x, b.y, b.z, b.w};
-  uint32_t o[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    o[i] = pack2_bf16(__uint_as_float(x[i] << 16) + __uint_as_float(y[i] << 16),
-                      __uint_as_float(x[i] & 0xffff0000u) + __uint_as_float(y[i] & 0xffff0000u));
-  return make_uint4(o[0], o[1], o[2], o[3]);
-}
+// affine_relu(v, ab, C6_C, part8) of tsg_mfma.h.
 
 // ---- backward sums of the BatchNorm in FRONT of the convolution, in the epilogue of its data gradient (round 6) ----------
 // The data gradient computed here is dy' of a BatchNorm -> ReLU pair (seg_oprs.py:39-46, resnet.py:36-46): SyncBN's backward
@@ -144,12 +116,12 @@ __global__ __launch_bounds__(256, OCC) void conv64_fwd_k(const bf16_t* __restric
   const int wm = wave & 1, wr = wave >> 1;
   if (AFF && tid < 2 * C6_C) abs_[tid] = in_ab[tid];      // visible after the first barrier of the tile loop
 
-  c6_bf16x8 fw[9][4];                                    // filter fragments: oc = 32 wm + p, ci = 16 kc + 8 half ..
+  bf16x8 fw[9][4];                                    // filter fragments: oc = 32 wm + p, ci = 16 kc + 8 half ..
 #pragma unroll
   for (int t = 0; t < 9; ++t)
 #pragma unroll
     for (int kc = 0; kc < 4; ++kc)
-      fw[t][kc] = *reinterpret_cast<const c6_bf16x8*>(w + ((wm * 32 + p) * 9 + t) * C6_C + kc * 16 + half * 8);
+      fw[t][kc] = *reinterpret_cast<const bf16x8*>(w + ((wm * 32 + p) * 9 + t) * C6_C + kc * 16 + half * 8);
 
   const int spl = tid >> 3, spart = tid & 7;             // store: tile column spl, 16-B part spart
   C6Lane ln;
@@ -172,7 +144,7 @@ __global__ __launch_bounds__(256, OCC) void conv64_fwd_k(const bf16_t* __restric
         uint4 v = rp[u];
         if (AFF) {
           const int ih = tp.oh0 - 1 + (ln.rc[u] & 0xff), iw = tp.ow0 - 1 + (ln.rc[u] >> 8);
-          if (ih >= 0 && ih < g.H && iw >= 0 && iw < g.W) v = c6_affine_relu(v, abs_, part8);
+          if (ih >= 0 && ih < g.H && iw >= 0 && iw < g.W) v = affine_relu(v, abs_, C6_C, part8);
         }
         *reinterpret_cast<uint4*>(patch + ((tid + 256 * u) >> 3) * C6_PS + part8) = v;
       }
@@ -183,7 +155,7 @@ __global__ __launch_bounds__(256, OCC) void conv64_fwd_k(const bf16_t* __restric
       if (OCC == 1) c6_fetch(x, g, tn, ln, part8, rp);
     }
 
-    c6_f32x16 acc[2];
+    f32x16 acc[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -195,15 +167,15 @@ __global__ __launch_bounds__(256, OCC) void conv64_fwd_k(const bf16_t* __restric
     // the last third of the loop.
     auto frag = [&](int s) {
       const int t = s >> 3, kc = (s >> 1) & 3, i = s & 1, kh = t / 3, kw = t % 3;
-      return *reinterpret_cast<const c6_bf16x8*>(pb + ((i + kh) * C6_PW + kw) * C6_PS + kc * 16);
+      return *reinterpret_cast<const bf16x8*>(pb + ((i + kh) * C6_PW + kw) * C6_PS + kc * 16);
     };
     constexpr int AHEAD = OCC == 1 ? C6_AHEAD : 4;       // two waves per SIMD hide most of the latency themselves
-    c6_bf16x8 ring[AHEAD];
+    bf16x8 ring[AHEAD];
 #pragma unroll
     for (int s = 0; s < AHEAD; ++s) ring[s] = frag(s);
 #pragma unroll
     for (int s = 0; s < 72; ++s) {
-      const c6_bf16x8 fb = ring[s % AHEAD];
+      const bf16x8 fb = ring[s % AHEAD];
       if (s + AHEAD < 72) ring[s % AHEAD] = frag(s + AHEAD);
       acc[s & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[s >> 3][(s >> 1) & 3], fb, acc[s & 1], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
@@ -242,7 +214,7 @@ __global__ __launch_bounds__(256, OCC) void conv64_fwd_k(const bf16_t* __restric
       if (tp.oh0 + qd < g.H && colok) {
         uint4 o = *reinterpret_cast<const uint4*>(outs + (qd * C6_TW + spl) * C6_PS + spart * 8);
         const int64_t off = ((int64_t)qd * g.W + spl) * C6_C + spart * 8;
-        if (addend) o = c6_add_bf16x8(o, ad[qd]);
+        if (addend) o = add_bf16x8(o, ad[qd]);
         *reinterpret_cast<uint4*>(yt + off) = o;
       }
     if (STATS) {
@@ -317,12 +289,12 @@ __global__ __launch_bounds__(256, 2) void conv64_dma_fwd_k(const bf16_t* __restr
     wred[tid] = 0.f; wred[256 + tid] = 0.f;
   }
 
-  c6_bf16x8 fw[9][4];                                    // filter fragments: oc = 32 wm + p, ci = 16 kc + 8 half ..
+  bf16x8 fw[9][4];                                    // filter fragments: oc = 32 wm + p, ci = 16 kc + 8 half ..
 #pragma unroll
   for (int t = 0; t < 9; ++t)
 #pragma unroll
     for (int kc = 0; kc < 4; ++kc)
-      fw[t][kc] = *reinterpret_cast<const c6_bf16x8*>(w + ((wm * 32 + p) * 9 + t) * C6_C + kc * 16 + half * 8);
+      fw[t][kc] = *reinterpret_cast<const bf16x8*>(w + ((wm * 32 + p) * 9 + t) * C6_C + kc * 16 + half * 8);
   const int spl = tid >> 3, spart = tid & 7;             // store: tile column spl, 16-B part spart
 
   // DMA: piece q = wave + 4 u; this lane's vector v = 64 q + lane = slot (v & 7) of patch pixel v >> 3.  Everything about
@@ -368,7 +340,7 @@ __global__ __launch_bounds__(256, 2) void conv64_dma_fwd_k(const bf16_t* __restr
       dma(tn, buf ^ 1);
     }
 
-    c6_f32x16 acc[2];
+    f32x16 acc[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -377,15 +349,15 @@ __global__ __launch_bounds__(256, 2) void conv64_dma_fwd_k(const bf16_t* __restr
     auto frag = [&](int s) {
       const int t = s >> 3, kc = (s >> 1) & 3, i = s & 1, kh = t / 3, kw = t % 3;
       const int off = (swz16[kw] ^ (((kc * 2) << 4) | (half << 4))) + pcol[kw];
-      return *reinterpret_cast<const c6_bf16x8*>(pbuf + off + (i + kh) * (C6_PW * 128));
+      return *reinterpret_cast<const bf16x8*>(pbuf + off + (i + kh) * (C6_PW * 128));
     };
     constexpr int AHEAD = 4;
-    c6_bf16x8 ring[AHEAD];
+    bf16x8 ring[AHEAD];
 #pragma unroll
     for (int s = 0; s < AHEAD; ++s) ring[s] = frag(s);
 #pragma unroll
     for (int s = 0; s < 72; ++s) {
-      const c6_bf16x8 fb = ring[s % AHEAD];
+      const bf16x8 fb = ring[s % AHEAD];
       if (s + AHEAD < 72) ring[s % AHEAD] = frag(s + AHEAD);
       acc[s & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[s >> 3][(s >> 1) & 3], fb, acc[s & 1], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
@@ -430,7 +402,7 @@ __global__ __launch_bounds__(256, 2) void conv64_dma_fwd_k(const bf16_t* __restr
       if (tp.oh0 + qd < g.H && colok) {
         uint4 o = *reinterpret_cast<const uint4*>(outs + (qd * C6_TW + spl) * C6_PS + spart * 8);
         const int64_t off = ((int64_t)qd * g.W + spl) * C6_C + spart * 8;
-        if (addend && !BSUM) o = c6_add_bf16x8(o, ad[qd]);
+        if (addend && !BSUM) o = add_bf16x8(o, ad[qd]);
         *reinterpret_cast<uint4*>(yt + off) = o;
         if (BSUM) c6_bsum_acc(bs, o, ad[qd], abm, spart * 8);
       }
@@ -530,12 +502,12 @@ __global__ __launch_bounds__(256, OCC) void conv64_fwd_s2_k(const bf16_t* __rest
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, p = lane & 31;
   const int wm = wave & 1, wr = wave >> 1;
   if (AFF && tid < 2 * C6_C) abs_[tid] = in_ab[tid];
-  c6_bf16x8 fw[9][4];
+  bf16x8 fw[9][4];
 #pragma unroll
   for (int t = 0; t < 9; ++t)
 #pragma unroll
     for (int kc = 0; kc < 4; ++kc)
-      fw[t][kc] = *reinterpret_cast<const c6_bf16x8*>(w + ((wm * 32 + p) * 9 + t) * C6_C + kc * 16 + half * 8);
+      fw[t][kc] = *reinterpret_cast<const bf16x8*>(w + ((wm * 32 + p) * 9 + t) * C6_C + kc * 16 + half * 8);
   const int part8 = (tid & 7) * 8;
   S2Lane<S2_NF, S2_NV, S2_PW> ln;
   ln.init(tid);
@@ -578,7 +550,7 @@ __global__ __launch_bounds__(256, OCC) void conv64_fwd_s2_k(const bf16_t* __rest
           if (u < S2_NF && (u < S2_NF - 1 || ln.rc[u] >= 0)) {
             const int pr = ln.rc[u] & 0xff, pc = ln.rc[u] >> 8;
             const int pix = pr * S2_PW + ((pc & 1) ? S2_NE + (pc >> 1) : (pc >> 1));
-            if (ok[k]) v[k] = c6_affine_relu(v[k], abs_, part8);
+            if (ok[k]) v[k] = affine_relu(v[k], abs_, C6_C, part8);
             *reinterpret_cast<uint4*>(patch + pix * C6_PS + part8) = v[k];
           }
         }
@@ -603,7 +575,7 @@ __global__ __launch_bounds__(256, OCC) void conv64_fwd_s2_k(const bf16_t* __rest
       tn = s2_tile(g, tile + gridDim.x, S2_TH, S2_TW);
       if (OCC == 1) fetch(tn);
     }
-    c6_f32x16 acc;
+    f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
@@ -612,7 +584,7 @@ __global__ __launch_bounds__(256, OCC) void conv64_fwd_s2_k(const bf16_t* __rest
       const bf16_t* pb = patch + ((2 * wr + kh) * S2_PW + (kw == 1 ? S2_NE + p : p + (kw >> 1))) * C6_PS + half * 8;
 #pragma unroll
       for (int kc = 0; kc < 4; ++kc) {
-        const c6_bf16x8 fb = *reinterpret_cast<const c6_bf16x8*>(pb + kc * 16);
+        const bf16x8 fb = *reinterpret_cast<const bf16x8*>(pb + kc * 16);
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[t][kc], fb, acc, 0, 0, 0);
       }
     }
@@ -684,12 +656,12 @@ __global__ __launch_bounds__(256, OCC) void conv64_dgrad_s2_k(const bf16_t* __re
     wred[tid] = 0.f; wred[256 + tid] = 0.f;
   }
   // transposed filter: wt[ci][kh'][kw'][co] = w[co][2 - kh'][2 - kw'][ci]; fragment of forward tap (kh, kw): rows ci, K = co
-  c6_bf16x8 fw[9][4];
+  bf16x8 fw[9][4];
 #pragma unroll
   for (int t = 0; t < 9; ++t)
 #pragma unroll
     for (int kc = 0; kc < 4; ++kc)
-      fw[t][kc] = *reinterpret_cast<const c6_bf16x8*>(wt + ((wm * 32 + p) * 9 + (8 - t)) * C6_C + kc * 16 + half * 8);
+      fw[t][kc] = *reinterpret_cast<const bf16x8*>(wt + ((wm * 32 + p) * 9 + (8 - t)) * C6_C + kc * 16 + half * 8);
   const int part8 = (tid & 7) * 8;
   S2Lane<D2_NF, D2_NV, D2_PW> ln;
   ln.init(tid);
@@ -725,7 +697,7 @@ __global__ __launch_bounds__(256, OCC) void conv64_dgrad_s2_k(const bf16_t* __re
 #pragma unroll
     for (int ph = 0; ph < 4; ++ph) {
       const int a = ph >> 1, b = ph & 1;
-      c6_f32x16 acc;
+      f32x16 acc;
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
@@ -736,7 +708,7 @@ __global__ __launch_bounds__(256, OCC) void conv64_dgrad_s2_k(const bf16_t* __re
           const int kw = b ? (iw ? 0 : 2) : 1, dc = b ? iw : 0;
 #pragma unroll
           for (int kc = 0; kc < 4; ++kc) {
-            const c6_bf16x8 fb = *reinterpret_cast<const c6_bf16x8*>(pb + (dr * D2_PW + dc) * C6_PS + kc * 16);
+            const bf16x8 fb = *reinterpret_cast<const bf16x8*>(pb + (dr * D2_PW + dc) * C6_PS + kc * 16);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[kh * 3 + kw][kc], fb, acc, 0, 0, 0);
           }
         }
@@ -833,7 +805,7 @@ static bool s2_geom(int64_t B, int64_t H, int64_t W, int th, int tw, S2Geom* g) 
 // 1: one prefetching block per CU.  Either way no spills: with __launch_bounds__(256, 2) AND the prefetch the compiler
 // spilled ~35 registers to scratch and the stride-1 kernel took 162 us.
 static int c6_occ() {
-  static const int occ = [] { const char* e = getenv("TSG_C64_OCC"); return e ? atoi(e) : 2; }();
+  static const int occ = tsg_env_int("TSG_C64_OCC", 2);
   return occ == 1 ? 1 : 2;
 }
 
@@ -878,7 +850,7 @@ int tsg_conv3x3_c64_fwd(const void* x, const void* w, void* y, float* partial, c
                                              (const bf16_t*)w, (bf16_t*)y, g, partial, in_ab, (const bf16_t*)addend)
   // TSG_CONV64_DMA=1|0 (default 1): the launches without normalise-on-load on conv64_dma_fwd_k (patch by LDS-DMA, double
   // buffered); needs two blocks per CU (occ 2) and 32-bit byte offsets into one image
-  static const bool use_dma = [] { const char* e = getenv("TSG_CONV64_DMA"); return !(e && e[0] == '0'); }();
+  static const bool use_dma = tsg_env_flag("TSG_CONV64_DMA", true);
   if (!in_ab && use_dma && occ == 2 && (int64_t)g.H * g.W * C6_C * 2 < 0x7fffffffLL) {
     if (partial) {
       TSG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv64_dma_fwd_k<true, false>),

@@ -13,14 +13,11 @@
 // image) is staged in LDS, and each lane gathers the 8 taps of its MFMA fragment from there.
 //
 // x: NCHW bf16 (any H, W).  y / dy: NHWC bf16 (channels_last).  w / dw: fp32 [64,3,3,3].
-#include "tsg_common.h"
+#include "tsg_mfma.h"
 
 namespace tsg {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 constexpr int DS_OC = 64;
 constexpr int DS_KP = 32;                      // padded GEMM-K: 27 taps + 5 zero

@@ -15,7 +15,7 @@
 // dil3_fwd_k<D, STATS> (forward; data gradient with the mode-1 filter):
 //   * conv3g_fwd_k's loop: implicit GEMM D[oc][pixel] += W[oc][tap, ci] X[tap, ci][pixel], 32x32x16 MFMAs, a 4-wave block
 //     owns 64 output channels x 8 x 32 pixels and walks C_in in chunks of 16, both LDS images double-buffered, the filter
-//     slab (fragment order, written by tsg_conv3x3_gen_prep_filter at tile width 64: the layout does not depend on the
+//     slab (fragment order of tsg_mfma.h, written by tsg_conv3x3_gen_prep_filter at tile width 64: independent of the
 //     dilation) by LDS-DMA, the patch through registers with predicated loads (zero padding), one barrier per chunk;
 //   * a wave computes 64 oc x 2 rows x 32 pixels; tap (kh, kw) of tile row r reads the pixel fragment at patch row
 //     r + d kh, column shift d kw: 18 fragment reads per chunk for the 36 MFMAs, one kernel row ahead of their use;
@@ -34,15 +34,9 @@
 // row, kh) with row + d kh = pr.  Next tile's operands are prefetched into registers by raw buffer loads (out-of-image
 // positions and channels beyond C_in carry an offset past num_records: zeros).  One block per CU (116,736 B of LDS at
 // d = 4).  Partials [pair][slot][64][9][64] are folded in fp64 in slot order by dil3_wrw_fold_k: no atomics, bit-equal runs.
-#include "tsg_common.h"
-#include <stdlib.h>
+#include "tsg_mfma.h"
 
 namespace tsg {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 dl_bf16x8;
-typedef __attribute__((ext_vector_type(16))) float dl_f32x16;
-typedef short dl_v4i16 __attribute__((ext_vector_type(4)));
-typedef dl_v4i16 __attribute__((address_space(3))) dl_lds_v4i16;
 
 constexpr int DL_TH = 8, DL_TW = 32;                     // output tile of the forward kernel
 constexpr int DL_KC = 16;                                // input channels per chunk
@@ -66,16 +60,6 @@ struct DlGeom {
   int B, H, W, Cin, Cout, Cst;                           // Cout: padded to 64 (the filter's), Cst: channels of y (its pitch)
   int tiles_h, tiles_w, ntiles, nchunks, noct, nslots;
 };
-
-__device__ __forceinline__ uint4 dl_add_bf16x8(uint4 a, uint4 b) {
-  const uint32_t x[4] = {a.x, a.y, a.z, a.w}, y[4] = {b.x, b.y, b.z, b.w};
-  uint32_t o[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    o[i] = pack2_bf16(__uint_as_float(x[i] << 16) + __uint_as_float(y[i] << 16),
-                      __uint_as_float(x[i] & 0xffff0000u) + __uint_as_float(y[i] & 0xffff0000u));
-  return make_uint4(o[0], o[1], o[2], o[3]);
-}
 
 template <int D, bool STATS>
 __global__ __launch_bounds__(256, 2) void dil3_fwd_k(const bf16_t* __restrict__ x, const bf16_t* __restrict__ wf,
@@ -141,7 +125,7 @@ __global__ __launch_bounds__(256, 2) void dil3_fwd_k(const bf16_t* __restrict__ 
         }
     };
 
-    dl_f32x16 acc[2][2];
+    f32x16 acc[2][2];
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -161,18 +145,18 @@ __global__ __launch_bounds__(256, 2) void dil3_fwd_k(const bf16_t* __restrict__ 
       const bf16_t* fa = fbuf + buf * DL_FELEMS + lane * 8;
       // the six pixel fragments of kernel row kh + 1 (2 tile rows x 3 column shifts) are read while the MFMAs of row kh
       // run, the filter fragments of tap t + 1 during tap t: two register sets each
-      dl_bf16x8 bq[2][2][3];                             // [kh & 1][row of the wave][kw]
+      bf16x8 bq[2][2][3];                             // [kh & 1][row of the wave][kw]
       auto read_row = [&](int kh) {
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
           for (int kw = 0; kw < 3; ++kw)
-            bq[kh & 1][i][kw] = *reinterpret_cast<const dl_bf16x8*>(pb + ((i + D * kh) * PW + D * kw) * PS);
+            bq[kh & 1][i][kw] = *reinterpret_cast<const bf16x8*>(pb + ((i + D * kh) * PW + D * kw) * PS);
       };
       read_row(0);
-      dl_bf16x8 af[2][2];
+      bf16x8 af[2][2];
 #pragma unroll
-      for (int j = 0; j < 2; ++j) af[0][j] = *reinterpret_cast<const dl_bf16x8*>(fa + (j * 64) * 8);
+      for (int j = 0; j < 2; ++j) af[0][j] = *reinterpret_cast<const bf16x8*>(fa + (j * 64) * 8);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int t = 0; t < 9; ++t) {
@@ -181,7 +165,7 @@ __global__ __launch_bounds__(256, 2) void dil3_fwd_k(const bf16_t* __restrict__ 
         if (t + 1 < 9) {
 #pragma unroll
           for (int j = 0; j < 2; ++j)
-            af[(t + 1) & 1][j] = *reinterpret_cast<const dl_bf16x8*>(fa + (((t + 1) * 2 + j) * 64) * 8);
+            af[(t + 1) & 1][j] = *reinterpret_cast<const bf16x8*>(fa + (((t + 1) * 2 + j) * 64) * 8);
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -216,7 +200,7 @@ __global__ __launch_bounds__(256, 2) void dil3_fwd_k(const bf16_t* __restrict__ 
       if (oh < g.H && ow < g.W && oct * DL_BN + part * 8 < g.Cst) {
         uint4 o = *reinterpret_cast<const uint4*>(outs + px * OS + part * 8);
         const int64_t off = ((int64_t)oh * g.W + ow) * g.Cst + part * 8;
-        if (addend) o = dl_add_bf16x8(o, *reinterpret_cast<const uint4*>(addend + img_off + off));
+        if (addend) o = add_bf16x8(o, *reinterpret_cast<const uint4*>(addend + img_off + off));
         *reinterpret_cast<uint4*>(yimg + off) = o;
         if (STATS) {                                     // the values just stored: no second pass over the tile
           const uint32_t w[4] = {o.x, o.y, o.z, o.w};
@@ -300,10 +284,10 @@ __global__ __launch_bounds__(256, 1) void dil3_wrw_k(const bf16_t* __restrict__ 
 #pragma unroll
   for (int u = 0; u < DW_TH; ++u) dyo[u] = (uint32_t)((((int64_t)u * g.W + spix) * g.Cout + spart * 8) * 2);
   const int chan = 16 * sub + 4 * (i16 & 3);
-  const dl_lds_v4i16* afr = (const dl_lds_v4i16*)(dyL + (8 * half + (i16 >> 2)) * DW_RBE + chan + 32 * wm);
-  const dl_lds_v4i16* bfr = (const dl_lds_v4i16*)(xL + (8 * half + (i16 >> 2)) * DW_RBE + chan + 32 * wh);
+  const lds_v4i16* afr = (const lds_v4i16*)(dyL + (8 * half + (i16 >> 2)) * DW_RBE + chan + 32 * wm);
+  const lds_v4i16* bfr = (const lds_v4i16*)(xL + (8 * half + (i16 >> 2)) * DW_RBE + chan + 32 * wh);
 
-  dl_f32x16 acc[9];
+  f32x16 acc[9];
 #pragma unroll
   for (int t = 0; t < 9; ++t)
 #pragma unroll
@@ -337,7 +321,7 @@ __global__ __launch_bounds__(256, 1) void dil3_wrw_k(const bf16_t* __restrict__ 
       rx[u] = make_uint4(v.x, v.y, v.z, v.w);
     }
   };
-  union Frag { dl_v4i16 q[2]; dl_bf16x8 v; };
+  union Frag { v4i16 q[2]; bf16x8 v; };
 
   int tile = slot;
   if (tile < g.ntiles) fetch(tile);
@@ -355,8 +339,8 @@ __global__ __launch_bounds__(256, 1) void dil3_wrw_k(const bf16_t* __restrict__ 
     Frag fa[8];
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) {
-      fa[ks].q[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((dl_lds_v4i16*)(afr + (ks * 16 + 0) * (DW_RBE / 4)));
-      fa[ks].q[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((dl_lds_v4i16*)(afr + (ks * 16 + 4) * (DW_RBE / 4)));
+      fa[ks].q[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16*)(afr + (ks * 16 + 0) * (DW_RBE / 4)));
+      fa[ks].q[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16*)(afr + (ks * 16 + 4) * (DW_RBE / 4)));
     }
 #pragma unroll
     for (int pr = 0; pr < P::PR; ++pr)
@@ -366,8 +350,8 @@ __global__ __launch_bounds__(256, 1) void dil3_wrw_k(const bf16_t* __restrict__ 
         for (int kw = 0; kw < 3; ++kw) {
           const int px = pr * P::PC + c * 16 + D * kw;   // patch pixel of the fragment's first K
           Frag fb;
-          fb.q[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((dl_lds_v4i16*)(bfr + (px + 0) * (DW_RBE / 4)));
-          fb.q[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((dl_lds_v4i16*)(bfr + (px + 4) * (DW_RBE / 4)));
+          fb.q[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16*)(bfr + (px + 0) * (DW_RBE / 4)));
+          fb.q[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16*)(bfr + (px + 4) * (DW_RBE / 4)));
 #pragma unroll
           for (int kh = 0; kh < 3; ++kh) {
             const int rr = pr - D * kh;

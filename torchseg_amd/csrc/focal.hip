@@ -19,8 +19,6 @@ template <int LT> __device__ __forceinline__ float lab_f(const void* p, int64_t 
 template <> __device__ __forceinline__ float lab_f<TSG_I64>(const void* p, int64_t i) { return (float)((const int64_t*)p)[i]; }
 template <> __device__ __forceinline__ float lab_f<TSG_U8>(const void* p, int64_t i) { return (float)((const uint8_t*)p)[i]; }
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
-
 template <typename T, int LT>
 __global__ __launch_bounds__(kT) void focal_fwd_k(const T* __restrict__ pred, const void* __restrict__ tgt,
                                                   int64_t P, float ignore, float gamma, float alpha,

@@ -17,15 +17,11 @@
 // fp32 inputs take the same kernels with bf16 hi/lo operand splitting
 // (a*b ~= ah*bh + ah*bl + al*bh, three accumulating passes, ~2^-16 relative),
 // which keeps the 1e-4 parity bar without an fp32 tensor-core path.
-#include "tsg_common.h"
+#include "tsg_mfma.h"
 #include <math.h>
-#include <stdlib.h>
 #include <string.h>
 
 namespace tsg {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int LDS_ROW = 72;                 // bf16 elements per padded tile row (144 B)
@@ -460,8 +456,6 @@ static int launch_gemm(const GemmArgs& g, int64_t batch, hipStream_t st) {
 //   dX       dX[c][i]  = sum_j dOut[c][j] P[i][j]    A = dOut NT   B = A     NT  EXPB 2
 //   dA       dP[i][j]  = sum_c X[c][i] dOut[c][j]    A = X    TR   B = dOut  TR  EPI 1
 // ---------------------------------------------------------------------------
-typedef short v4i16 __attribute__((ext_vector_type(4)));
-typedef v4i16 __attribute__((address_space(3))) lds_v4i16;
 
 constexpr int MM_BK = 64, MM_T = 256;
 constexpr int MM_NT_ROW = 72;                       // elements per NT row (64 + 8 pad)
@@ -979,7 +973,7 @@ static int launch_mm_cfg(MmArgs g, hipStream_t st) {
   const int64_t tiles = (int64_t)g.tiles_m * g.tiles_n * g.batch;
   g.per_xcd = (int)((tiles + 7) / 8);
   { const char* o = getenv("TSG_PSA_ORDER"); g.m_fastest = (o && o[0] == 'm') ? 1 : 0; }
-  { const char* o = getenv("TSG_PSA_ABLATE"); g.ablate = o ? atoi(o) : 0; }
+  g.ablate = tsg_env_int("TSG_PSA_ABLATE", 0);
   constexpr size_t lds_bytes = MmGeom<BM, BN>::LDS;
   TSG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&psa_mm<BM, BN, PF, A_TR, B_TR, EXPB, EPI, SPLIT, AF, UT>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
@@ -1038,7 +1032,7 @@ static int launch_mm(MmArgs g, hipStream_t st) {
     // them with two sets of untracked prefetch instead: measured 151 vs 141-147 us for the backward call (three sets at one
     // block per CU: 193 us) -- with 8 K tiles per output tile dA is not bound by the depth of its K pipeline
     if constexpr (A_TR) {
-      static const int ut_pf = [] { const char* e = getenv("TSG_PSA_UT_PF"); return e ? atoi(e) : 1; }();
+      static const int ut_pf = tsg_env_int("TSG_PSA_UT_PF", 1);
       if (ut_pf == 2) return launch_mm_cfg<128, 64, 2, A_TR, B_TR, EXPB, EPI, true, false, true>(g, st);
     }
     return launch_mm_cfg<128, 64, 1, A_TR, B_TR, EXPB, EPI, true>(g, st);
@@ -1132,8 +1126,8 @@ static int colstat(const T* A, int64_t B, int64_t K, int64_t N, PsaWs& w, float*
                    const int* run_if = nullptr) {
   constexpr int V = sizeof(T) == 2 ? 8 : 4;
   if (N % V == 0 && aligned16(A)) {
-    static const int want = [] { const char* e = getenv("TSG_PSA_COLCHUNKS"); const int v = e ? atoi(e) : kChunks;
-                                 return v < 1 ? 1 : (v > kChunks ? kChunks : v); }();
+    static const int env = tsg_env_int("TSG_PSA_COLCHUNKS", kChunks);
+    const int want = env < 1 ? 1 : (env > kChunks ? kChunks : env);
     const int rpc = (int)((K + want - 1) / want);
     const int nch = (int)((K + rpc - 1) / rpc);                        // chunks that actually hold rows
     const int64_t nv = N / V;
@@ -1209,7 +1203,7 @@ int tsg_psa_fwd(const void* X, const void* A, void* out, float* lse, int dtype, 
     // safe while the column sums stay in [1e-20, 1e20] (|logit| up to ~46); a tile that sees anything else raises a device
     // flag, and the three launches of the classic path that follow — each returns at once unless the flag is set —
     // recompute the whole call exactly as round 3 did.  No host synchronisation either way.
-    static const bool optimistic = [] { const char* o = getenv("TSG_PSA_OPTIMISTIC"); return !(o && o[0] == '0'); }();
+    static const bool optimistic = tsg_env_flag("TSG_PSA_OPTIMISTIC", true);
     if (optimistic && mm_cfg() / 10000000 == 7 && mm_cfg() != 71280642 && w.Af) {
       if ((e = af_prepare(m, w.Af, st, w.flag))) return e;             // psa_frag_k also clears the flag
       MmArgs o = m;

@@ -3,7 +3,7 @@
 // decay per group, dampening 0, no nesterov):
 //   g = grad*grad_scale + wd*p ; buf = first ? g : momentum*buf + g ; p -= lr*buf
 // One read of (p, grad, buf), one write of (p, buf): 20 B/element, HBM-bound.
-#include "tsg_common.h"
+#include "tsg_mfma.h"
 
 namespace tsg {
 __global__ __launch_bounds__(256) void sgd_k(float* __restrict__ p, const float* __restrict__ g,
@@ -95,7 +95,6 @@ extern "C" int tsg_sgd_step(float* param, const float* grad, float* momentum_buf
   TSG_CHECK_LAUNCH();
   return 0;
 }
-
 
 // ---------------------------------------------------------------- multi-tensor step
 // One launch for up to TSG_SGD_MAX_SEGS parameter tensors: the pointer table travels by value in the kernel
@@ -199,7 +198,6 @@ extern "C" int tsg_sgd_multi_step_dev(const uint64_t* params, const uint64_t* gr
   return 0;
 }
 
-
 // ---------------------------------------------------------------- multi-tensor copy (gradient -> DDP bucket)
 namespace tsg {
 struct CopySegs {
@@ -248,7 +246,6 @@ extern "C" int tsg_multi_copy_f32(const uint64_t* src, const uint64_t* dst, cons
   return 0;
 }
 
-
 // ---------------------------------------------------------------- bf16 shadows of the fp32 master filters
 // The convolutions compute in bf16 (autocast), so every step each fp32 filter used to be cast to bf16 again (one tiny
 // launch per convolution) and, for the layers whose data gradient runs as a forward convolution, rotated / transposed
@@ -260,19 +257,11 @@ struct ShadowEntry {
   const float* w;
   bf16_t* wb;
   bf16_t* wrt;
-  bf16_t* wf0;        // round 5: the filter in MFMA fragment order for tsg_conv3x3_gen_fwd (g3_prep_filter_k mode 0), or 0
+  bf16_t* wf0;        // round 5: the filter in MFMA fragment order for tsg_conv3x3_gen_fwd (tsg_mfma.h: frag_offset; mode 0), or 0
   bf16_t* wf1;        // ... and for the data gradient (mode 1: rot180 + transpose; tile width bn1 = 32 for tsg_conv3x3_s2_dgrad)
   int n, O, I, bn0, bn1, pad;
 };
 static_assert(sizeof(ShadowEntry) == 64, "layout shared with torchseg_amd/shadow.py");
-
-// element offset of W'[oc][tap][ci] in the fragment-order image of csrc/conv3g.hip (g3_prep_filter_k):
-//   out[oc tile][chunk][tap][ocb][lane][e],  oc = tile BN + ocb 32 + (lane & 31),  ci = chunk 16 + (lane >> 5) 8 + e
-__device__ __forceinline__ int64_t g3_frag_offset(int oc, int tap, int ci, int Ci, int BN) {
-  const int nch = Ci >> 4, ocb_n = BN >> 5;
-  const int tile = oc / BN, rem = oc - tile * BN, ocb = rem >> 5, ln = ((ci >> 3) & 1) * 32 + (rem & 31);
-  return ((((int64_t)(tile * nch + (ci >> 4)) * 9 + tap) * ocb_n + ocb) * 64 + ln) * 8 + (ci & 7);
-}
 
 // map[block] = {entry, chunk | kind << 28}.  kind 0: 4096 SOURCE elements of the entry -> wb, wrt, wf0 (and wf1, when the host
 // asks for it there: TSG_SHADOW_WF1_PASS=0).  kind 1 (round 6): 4096 DESTINATION elements of wf1.  Walking the source, the data-
@@ -290,16 +279,10 @@ __global__ __launch_bounds__(256) void weight_shadow_k(const ShadowEntry* __rest
   const int end = base + kSgdChunk < e.n ? base + kSgdChunk : e.n;
   const int tapI = 9 * e.I;
   if (kind == 1) {                                     // e.n = 9 O I elements of wf1, 8 per thread and round
-    const int nch = e.O >> 4, ocb_n = e.bn1 >> 5;
     for (int d = base + threadIdx.x * 8; d < end; d += 256 * 8) {
-      const int ln = (d >> 3) & 63;
-      int rest = d >> 9;
-      const int ocb = rest % ocb_n; rest /= ocb_n;
-      const int tp = rest % 9; rest /= 9;
-      const int c16 = rest % nch, tile = rest / nch;
-      const int ci = tile * e.bn1 + ocb * 32 + (ln & 31);              // W'[ci][tp][o] = w[o][8 - tp][ci]
-      const int o0 = c16 * 16 + (ln >> 5) * 8;
-      const float* src = e.w + ((int64_t)o0 * 9 + (8 - tp)) * e.I + ci;
+      const FragPos p = frag_decode(d >> 3, e.O >> 4, e.bn1 >> 5);
+      const int ci = p.oc(e.bn1), o0 = p.ci0();                        // W'[ci][tp][o] = w[o][8 - tp][ci]
+      const float* src = e.w + ((int64_t)o0 * 9 + (8 - p.tap)) * e.I + ci;
       uint32_t pk[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j)
@@ -309,15 +292,10 @@ __global__ __launch_bounds__(256) void weight_shadow_k(const ShadowEntry* __rest
     return;
   }
   if (kind == 2) {                                     // the FORWARD image by destination: W'[oc][tp][ci0 .. ci0 + 7] = w[oc][tp][ci0 ..]
-    const int nch = e.I >> 4, ocb_n = e.bn0 >> 5;
     for (int d = base + threadIdx.x * 8; d < end; d += 256 * 8) {
-      const int ln = (d >> 3) & 63;
-      int rest = d >> 9;
-      const int ocb = rest % ocb_n; rest /= ocb_n;
-      const int tp = rest % 9; rest /= 9;
-      const int c16 = rest % nch, tile = rest / nch;
-      const int oc = tile * e.bn0 + ocb * 32 + (ln & 31), ci0 = c16 * 16 + (ln >> 5) * 8;
-      const float4* src = reinterpret_cast<const float4*>(e.w + ((int64_t)oc * 9 + tp) * e.I + ci0);
+      const FragPos p = frag_decode(d >> 3, e.I >> 4, e.bn0 >> 5);
+      const int oc = p.oc(e.bn0), ci0 = p.ci0();
+      const float4* src = reinterpret_cast<const float4*>(e.w + ((int64_t)oc * 9 + p.tap) * e.I + ci0);
       const float4 a = src[0], b = src[1];
       *reinterpret_cast<uint4*>(e.wf0 + d) = make_uint4(
           (uint32_t)f32_to_bf16(a.x) | ((uint32_t)f32_to_bf16(a.y) << 16), (uint32_t)f32_to_bf16(a.z) | ((uint32_t)f32_to_bf16(a.w) << 16),
@@ -334,8 +312,8 @@ __global__ __launch_bounds__(256) void weight_shadow_k(const ShadowEntry* __rest
     if (geo) {                                         // w is [O][3][3][I] (a channels_last 3x3 filter)
       const int o = i / tapI, r = i - o * tapI, tap = r / e.I, ci = r - tap * e.I;
       if (e.wrt) e.wrt[(ci * 9 + (8 - tap)) * e.O + o] = v;
-      if (wf0_here) e.wf0[g3_frag_offset(o, tap, ci, e.I, e.bn0)] = v;          // W' = w: C_out' = O, C_in' = I
-      if (wf1_here) e.wf1[g3_frag_offset(ci, 8 - tap, o, e.O, e.bn1)] = v;      // W'[ci][8 - tap][o] = w[o][tap][ci]
+      if (wf0_here) e.wf0[frag_offset(o, tap, ci, e.I, e.bn0)] = v;          // W' = w: C_out' = O, C_in' = I
+      if (wf1_here) e.wf1[frag_offset(ci, 8 - tap, o, e.O, e.bn1)] = v;      // W'[ci][8 - tap][o] = w[o][tap][ci]
     }
   }
 }

@@ -22,12 +22,9 @@
 //             in a fixed order (fp64) => deterministic, no atomics.
 //
 // x: NCHW bf16.  y / dy: NHWC bf16 (channels_last).  w / dw: fp32 [64,3,7,7].
-#include "tsg_common.h"
+#include "tsg_mfma.h"
 
 namespace tsg {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 constexpr int SC_OC = 64;
 constexpr int SC_KP = 176;             // padded GEMM-K: 22 rows x 8 slots
@@ -105,13 +102,6 @@ __device__ __forceinline__ void fetch_patch(const bf16_t* __restrict__ x, const 
   }
 }
 
-typedef __attribute__((ext_vector_type(2))) float f32x2_t;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-__device__ __forceinline__ uint32_t pack_bf16(float a, float b) {      // v_cvt_pk_bf16_f32: round to nearest even
-  const f32x2_t f = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, bf16x2_t));
-}
-
 // ---------------------------------------------------------------- forward
 // 4 waves: wave = (row pair wr) * 2 + (oc half wm).  A wave keeps the weights of its 32 output channels in
 // registers (11 K-fragments) and runs two pixel rows against them.
@@ -183,8 +173,8 @@ __global__ __launch_bounds__(256) void stem_fwd_k(const bf16_t* __restrict__ x, 
       for (int gq = 0; gq < 4; ++gq) {
         const int oc0 = 32 * wm + 8 * gq + 4 * half;
         uint2 v;
-        v.x = pack_bf16(acc[i][4 * gq + 0], acc[i][4 * gq + 1]);
-        v.y = pack_bf16(acc[i][4 * gq + 2], acc[i][4 * gq + 3]);
+        v.x = pack2_bf16(acc[i][4 * gq + 0], acc[i][4 * gq + 1]);
+        v.y = pack2_bf16(acc[i][4 * gq + 2], acc[i][4 * gq + 3]);
         *reinterpret_cast<uint2*>(outs + ((2 * wr + i) * SC_TW + p) * 72 + oc0) = v;
       }
     __syncthreads();
@@ -327,7 +317,7 @@ __global__ __launch_bounds__(256, 3) void stem_wrw_k(const bf16_t* __restrict__ 
               const float a = bps[c], dv = fmaf(xv, a, bps[SC_OC + c]) > 0.f ? dav : 0.f;
               o2[h] = fmaf(a, dv, fmaf(bps[3 * SC_OC + c], xv - bps[2 * SC_OC + c], bps[4 * SC_OC + c]));
             }
-            wd[i] = pack_bf16(o2[0], o2[1]);
+            wd[i] = pack2_bf16(o2[0], o2[1]);
           }
         }
         rd[q] = make_uint4(wd[0], wd[1], wd[2], wd[3]);
@@ -414,7 +404,6 @@ __global__ __launch_bounds__(256) void stem_wrw_fold(const float* __restrict__ p
   }
 }
 
-
 // =====================================================================================================================
 // Round 6: the ResNet stem WITHOUT its 537 MB activation (furnace/base_model/resnet.py:96-100,131-133:
 // maxpool(relu(bn1(conv1(img))))).  The 3 -> 64 7x7/2 convolution is 79 GFLOP = ~40 us of MFMA over a 100 MB image, its
@@ -457,8 +446,8 @@ __device__ __forceinline__ void stem_tile_to_lds(const uint32_t* __restrict__ pa
     for (int gq = 0; gq < 4; ++gq) {
       const int oc0 = 32 * wm + 8 * gq + 4 * half;
       uint2 v;
-      v.x = pack_bf16(acc[i][4 * gq + 0], acc[i][4 * gq + 1]);
-      v.y = pack_bf16(acc[i][4 * gq + 2], acc[i][4 * gq + 3]);
+      v.x = pack2_bf16(acc[i][4 * gq + 0], acc[i][4 * gq + 1]);
+      v.y = pack2_bf16(acc[i][4 * gq + 2], acc[i][4 * gq + 3]);
       *reinterpret_cast<uint2*>(outs + ((2 * wr + i) * SC_TW + p) * 72 + oc0) = v;
     }
 }
@@ -735,7 +724,7 @@ __global__ __launch_bounds__(256, WAVES) void stem_wrw_pool_k(const bf16_t* __re
           }
         }
 #pragma unroll
-        for (int q = 0; q < 4; ++q) dyw[q][i] = ok[q] ? pack_bf16(o2[q][0], o2[q][1]) : 0u;
+        for (int q = 0; q < 4; ++q) dyw[q][i] = ok[q] ? pack2_bf16(o2[q][0], o2[q][1]) : 0u;
       }
 #pragma unroll
       for (int rs = 0; rs < 2; ++rs) {                 // rows 2 kk + rs: pixel pair (2 m, 2 m + 1) -> one 32-bit LDS write per channel
@@ -882,8 +871,8 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_pool_k(const bf16_t* __restri
           for (int gq = 0; gq < 4; ++gq) {
             const int oc0 = 32 * wm + 8 * gq + 4 * half;
             uint2 v;
-            v.x = pack_bf16(acc[i][4 * gq + 0], acc[i][4 * gq + 1]);
-            v.y = pack_bf16(acc[i][4 * gq + 2], acc[i][4 * gq + 3]);
+            v.x = pack2_bf16(acc[i][4 * gq + 0], acc[i][4 * gq + 1]);
+            v.y = pack2_bf16(acc[i][4 * gq + 2], acc[i][4 * gq + 3]);
             *reinterpret_cast<uint2*>(outs + ((i0 + i) * SC_TW + p) * 72 + oc0) = v;
           }
         }
@@ -932,7 +921,7 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_pool_k(const bf16_t* __restri
       }
       uint32_t ov[4], w[2] = {0u, 0u};
 #pragma unroll
-      for (int j = 0; j < 4; ++j) ov[j] = pack_bf16(best[2 * j], best[2 * j + 1]);
+      for (int j = 0; j < 4; ++j) ov[j] = pack2_bf16(best[2 * j], best[2 * j + 1]);
 #pragma unroll
       for (int j = 0; j < 8; ++j) w[j >> 2] |= (uint32_t)am[j] << (8 * (j & 3));
       const int64_t o = (((int64_t)tp.b * pg.PH + ph) * pg.PW + pwx) * SC_OC + spart * 8;

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include "../../include/tsg_hip.h"
 
 #define TSG_WAVE 64
@@ -189,7 +190,50 @@ __device__ __forceinline__ void block_sum2(float& a, float& b, float* sm) {
   }
 }
 
+// Block-wide sum of two doubles: as above, `sm` needs 2 * (blockDim.x / 64) doubles.
+__device__ __forceinline__ void block_sum2(double& a, double& b, double* sm) {
+  a = wave_sum(a);
+  b = wave_sum(b);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  if (lane == 0) { sm[2 * w] = a; sm[2 * w + 1] = b; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double ta = 0.0, tb = 0.0;
+    for (int i = 0; i < nw; ++i) { ta += sm[2 * i]; tb += sm[2 * i + 1]; }
+    a = ta; b = tb;
+  }
+}
+
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
+
+// V consecutive per-channel floats starting at c0 (c0 % V == 0 => 16-B aligned)
+template <int V>
+__device__ __forceinline__ void ldc(const float* __restrict__ p, int64_t c0, float (&o)[V]) {
+  if (V == 1) {
+    o[0] = p[c0];
+  } else {
+#pragma unroll
+    for (int q = 0; q < V / 4; ++q) {
+      const float4 t = *reinterpret_cast<const float4*>(p + c0 + 4 * q);
+      o[4 * q + 0] = t.x; o[4 * q + 1] = t.y; o[4 * q + 2] = t.z; o[4 * q + 3] = t.w;
+    }
+  }
+}
+
 static inline int ceil_div_i(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 
 }  // namespace tsg
+
+// Environment switches of the launchers.  tsg_env_int: atoi of the variable, `def` when it is unset.  tsg_env_flag: a
+// switch that is on by default is off only for a value that starts with '0'; one that is off by default is on only for a
+// value that starts with '1'.  A launcher that reads its switch once per process keeps the result in a `static const`;
+// one whose switch the tests flip inside a process calls these on every launch.
+static inline int tsg_env_int(const char* name, int def) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : def;
+}
+static inline bool tsg_env_flag(const char* name, bool def) {
+  const char* e = getenv(name);
+  return def ? !(e && e[0] == '0') : (e && e[0] == '1');
+}

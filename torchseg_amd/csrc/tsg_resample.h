@@ -42,4 +42,16 @@ __device__ __forceinline__ float tap_weight(float scale, int dst, int in_size, i
   return w;
 }
 
+// Half-pixel-centre bilinear taps (cv2.resize INTER_LINEAR == F.interpolate(align_corners=False), no antialiasing), for
+// augment.hip's random-scale crop and upsample.hip's evaluator resize: src = (dst + 0.5) * scale - 0.5 in double as cv2
+// computes it, the weight narrowed afterwards; i0 = floor(src), border taps clamped with weight 0 (OpenCV resize.cpp).
+__device__ __forceinline__ void hp_index(int dst, double scale, int in, int& i0, int& i1, float& w) {
+  const double src = ((double)dst + 0.5) * scale - 0.5;
+  int s = (int)floor(src);
+  float f = (float)(src - (double)s);
+  if (s < 0) { s = 0; f = 0.f; }
+  if (s >= in - 1) { s = in - 1; f = 0.f; }
+  i0 = s; i1 = s + 1 < in ? s + 1 : in - 1; w = f;
+}
+
 }  // namespace tsg

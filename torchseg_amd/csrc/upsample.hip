@@ -436,16 +436,8 @@ using namespace tsg;
 // antialiasing): what the evaluator applies to the class scores of every scale (furnace/engine/evaluator.py:250-252:
 // cv2.resize(score, (ori_cols, ori_rows), interpolation=cv2.INTER_LINEAR)).  src = (dst + 0.5) * in / out - 0.5,
 // i0 = floor(src), border taps clamped with weight 0 (OpenCV resize.cpp).  Planar [NC, IH, IW] -> [NC, OH, OW]; up- or
-// down-sampling.  `accumulate` adds into y (the sum over scales of sliding_eval, evaluator.py:196-199).
-__device__ __forceinline__ void hp_index(int dst, double scale, int in, int& i0, int& i1, float& w) {
-  const double src = ((double)dst + 0.5) * scale - 0.5;
-  int s = (int)floor(src);
-  float f = (float)(src - (double)s);
-  if (s < 0) { s = 0; f = 0.f; }
-  if (s >= in - 1) { s = in - 1; f = 0.f; }
-  i0 = s; i1 = s + 1 < in ? s + 1 : in - 1; w = f;
-}
-
+// down-sampling.  `accumulate` adds into y (the sum over scales of sliding_eval, evaluator.py:196-199).  Taps: hp_index
+// (tsg_resample.h).
 template <typename T, bool ACC>
 __global__ __launch_bounds__(kT) void resize_hp_k(const T* __restrict__ x, float* __restrict__ y, int64_t NC, int IH,
                                                   int IW, int OH, int OW) {

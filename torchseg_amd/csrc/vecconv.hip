@@ -9,14 +9,11 @@
 //   forward   y[b][o]   = sum_ci x[b][ci] w[o][ci]                 M = b, N = o,  K = ci
 //   data      dx[b][ci] = sum_o  dy[b][o] w[o][ci]                 M = b, N = ci, K = o
 //   weight    dw[o][ci] = sum_b  dy[b][o] x[b][ci]   (fp32 out)    M = o, N = ci, K = b
-#include "tsg_common.h"
+#include "tsg_mfma.h"
 
 namespace tsg {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 vc_bf16x8;
-typedef __attribute__((ext_vector_type(16))) float vc_f32x16;
-
-union VcFrag { uint32_t u[4]; uint4 q; vc_bf16x8 v; };
+union VcFrag { uint32_t u[4]; uint4 q; bf16x8 v; };
 
 __device__ __forceinline__ VcFrag vc_zero() { VcFrag f; f.q = make_uint4(0u, 0u, 0u, 0u); return f; }
 
@@ -33,7 +30,7 @@ __global__ __launch_bounds__(64) void vec1x1_fwd_k(const bf16_t* __restrict__ x,
                                                    bf16_t* __restrict__ y, int B, int Cin, int Cout) {
   const int lane = threadIdx.x, n = lane & 31, half = lane >> 5;
   const int o = blockIdx.x * 32 + n;
-  vc_f32x16 acc;
+  f32x16 acc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll 4
@@ -58,7 +55,7 @@ __global__ __launch_bounds__(64) void vec1x1_bwd_k(const bf16_t* __restrict__ dy
                                                    float* __restrict__ dw, int B, int Cin, int Cout, int ntw) {
   const int lane = threadIdx.x, n = lane & 31, half = lane >> 5;
   const int cit = (Cin + 31) / 32;
-  vc_f32x16 acc;
+  f32x16 acc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
   if ((int)blockIdx.x < ntw) {
@@ -127,7 +124,6 @@ struct VcBnArgs {
 };
 
 __device__ __forceinline__ float vc_bf16r(float v) { return __uint_as_float(pack2_bf16(v, 0.f) << 16); }
-__device__ __forceinline__ float vc_sigmoid(float v) { return 1.f / (1.f + expf(-v)); }
 
 template <int BNMODE, int ACT>
 __global__ __launch_bounds__(64) void vec1x1_bnact_fwd_k(const bf16_t* __restrict__ x, const float* __restrict__ w,
@@ -135,7 +131,7 @@ __global__ __launch_bounds__(64) void vec1x1_bnact_fwd_k(const bf16_t* __restric
                                                          int Cout, VcBnArgs bn) {
   const int lane = threadIdx.x, n = lane & 31, half = lane >> 5;
   const int o = blockIdx.x * 32 + n;
-  vc_f32x16 acc;
+  f32x16 acc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll 4
@@ -190,7 +186,7 @@ __global__ __launch_bounds__(64) void vec1x1_bnact_fwd_k(const bf16_t* __restric
         } else if (ACT == 1) {
           t = t > 0.f ? t : 0.f;
         }
-        if (ACT == 2) t = vc_sigmoid(t);
+        if (ACT == 2) t = sigmoidf_(t);
         out[(int64_t)bb * Cout + o] = (bf16_t)(pack2_bf16(t, 0.f) & 0xffffu);
       }
     }
@@ -297,7 +293,7 @@ __global__ __launch_bounds__(256) void vec1x1_bnact_bwd_k(const bf16_t* __restri
   }
   __syncthreads();
   if (threadIdx.x >= 64) return;                                    // phase 2, one wave: the MFMAs
-  vc_f32x16 acc;
+  f32x16 acc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
   if (wtile) {

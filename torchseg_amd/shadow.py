@@ -182,7 +182,7 @@ class _Bank(object):
 
 
     def get_gen(self, param, mode, bn):
-        """The filter of `param` ([O, I, 3, 3] channels_last fp32 master) in the MFMA fragment order of csrc/conv3g.hip
+        """The filter of `param` ([O, I, 3, 3] channels_last fp32 master) in the MFMA fragment order of csrc/tsg_mfma.h
         (what tsg_conv3x3_gen_prep_filter writes: mode 0 forward, mode 1 data gradient; `bn` = tile width), kept fresh by
         the same one launch per optimizer step as the plain bf16 casts — 32 preparation launches per BiSeNet step gone."""
         e = self.register(param, False)
