@@ -543,6 +543,13 @@ int tsg_ohem_up_bwd(const void* z, int dtype, const void* labels, int ltype,
                     const float* gscale, void* dz,
                     void* ws, size_t ws_bytes, void* stream);
 
+/* The same two entry points for 33 <= C <= 256 classes (ADE20K: 150): tsg_ohem_up_wide_supported() != 0 when
+ * tsg_ohem_up_fwd / _bwd take the shape on the class-chunked kernels (ohem_upw_fwd_k: online softmax state per output
+ * row carried over chunks of <= 32 classes; ohem_upw_bwd_k: one block per class chunk) under the geometry limits of
+ * the narrow path.  tsg_ohem_up_supported() keeps answering 0 for C > 32, so a caller opts in to the wide kernels by
+ * asking this function.  Same outputs, same selection tail, same determinism. */
+int tsg_ohem_up_wide_supported(int C, int IH, int IW, int OH, int OW);
+
 /* prob[P] = the target-class probability the selection ranks (mask_prob of loss_opr.py:81-83): exp(-nll) evaluated
  * by the same device expression the OHEM kernels use, 1 for ignored pixels.  With it the selection contract is
  * checkable bit for bit: thr == sort(prob)[k-1] and kept == valid & (prob <= thr). */

@@ -1,0 +1,345 @@
+"""The fused upsample + cross-entropy head for 33..256 classes (ohem_upw_fwd_k / ohem_upw_bwd_k behind
+TSG_FUSE_HEAD_WIDE; ADE20K: 150 classes).  Inputs from the generator of tests/test_fused_head_gpu.py, the oracle is
+oracle.ohem_ref.ohem_cross_entropy on the CPU F.interpolate of the same z, the bounds are the ones that file uses for this
+arithmetic in fp32: loss 1e-4 * max(1, |ref|), max |dz - ref| <= 2e-4 * max |ref grad|, branch and valid count exact.
+Every test flips losses.FUSE_HEAD_WIDE with monkeypatch."""
+import functools
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import _guard
+from oracle import ohem_ref
+from test_fused_head_gpu import _make
+
+pytestmark = pytest.mark.gpu
+
+PLAIN = [  # B, C, IH, IW, OH, OW, regime
+    (2, 33, 8, 8, 64, 64, "random"),                 # one full chunk plus one class
+    (2, 150, 9, 7, 36, 28, "confident"),             # x4 (16-class chunks), ragged, OW % 4 != 0
+    (1, 150, 40, 36, 320, 288, "confident"),         # two column tiles, several row bands
+    (2, 150, 60, 60, 480, 480, "confident"),         # PSANet's own head shape
+    (1, 256, 8, 8, 64, 64, "random"),                # label 255 is a class index here
+]
+
+
+def _seed(case):
+    return case[2] * 7 + case[5]
+
+
+def _labels(t, kind, cuda):
+    return t.to(torch.uint8 if kind == "u8" else torch.int64).to(cuda)
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle(case, ignore, thresh, min_kept, wseed=None, redraw=False):
+    """(z, t, weight, ref loss, info, ref dz): computed once per case on the CPU and shared"""
+    B, C, IH, IW, OH, OW, regime = case
+    z, t = _trained(B, C, IH, OH) if regime == "trained" else _make(B, C, IH, IW, OH, OW, regime, seed=_seed(case))
+    if redraw:                                       # 255 a real class: the ignored pixels get another value
+        t = t.clone()
+        t[:, -2:] = ignore
+    w = None
+    if wseed is not None:
+        w = torch.rand(C, generator=torch.Generator().manual_seed(wseed)) * 3.0 + 0.25
+    zr = z.clone().requires_grad_(True)
+    logits = F.interpolate(zr, size=(OH, OW), mode="bilinear", align_corners=True)
+    loss, info = ohem_ref.ohem_cross_entropy(logits, t, ignore, thresh, min_kept, w, return_info=True)
+    loss.backward()
+    return z, t, w, loss.detach(), info, zr.grad
+
+
+# The k-th-value branch keeps exactly min_kept = 2048 pixels of mean nll 0.9 here, so ONE pixel changing sides moves the
+# loss by 4e-4, four times the loss bound: the case can only be judged where the oracle's own threshold is isolated.  The
+# device and the CPU evaluate p_t = exp(-(lse - x_t)) from logits of magnitude ~20 in two fp32 orders: a few ulp of 20
+# (1.9e-6 each) in nll, i.e. up to ~1e-5 relative in p_t (tests/test_fused_head_gpu.py bounds the same quantity by 2e-5).
+# With the file's own seed (IH + len("trained") = 15) the CPU finds 9 pixels within 2e-5 * thr of its threshold, two of them
+# within 4e-7 * thr; seed 291 is the first in [15, 400) whose 2e-5 band holds the k-th pixel alone (CPU figures only: branch
+# 1, threshold 0.995599).  The test asserts that property of the oracle before it looks at the device.
+_TRAINED_SEED = 291
+
+
+def _trained(B, C, IH, S):
+    """the "trained" generator of tests/test_fused_head_gpu.py (labels constant over quadrants, 2 % re-drawn) with
+    z = randn + 12 * onehot"""
+    g = torch.Generator().manual_seed(_TRAINED_SEED)
+    quad = torch.randint(0, C, (B, 2, 2), generator=g)
+    lab_lo = quad.repeat_interleave(IH // 2, 1).repeat_interleave(IH // 2, 2)
+    t = lab_lo.repeat_interleave(S // IH, 1).repeat_interleave(S // IH, 2)
+    flip = torch.rand(t.shape, generator=g) < 0.02
+    t = torch.where(flip, torch.randint(0, C, t.shape, generator=g), t)
+    z = torch.randn(B, C, IH, IH, generator=g) + 12.0 * F.one_hot(lab_lo, C).permute(0, 3, 1, 2).float()
+    t[:, : max(1, S // 16)] = 255
+    return z.contiguous(), t
+
+
+class _Spy:
+    """counts the provider calls a criterion makes (instance-level, removed on exit)"""
+    NAMES = ("ohem_up_fwd", "ohem_up_bwd", "upsample_fwd", "upsample_bwd", "ohem_fwd", "ohem_bwd")
+
+    def __init__(self):
+        from torchseg_amd import kernels as K
+        self.kp, self.calls = K.provider(), {n: 0 for n in self.NAMES}
+
+    def __enter__(self):
+        for n in self.NAMES:
+            fn = getattr(self.kp, n)
+            setattr(self.kp, n, (lambda name, f: lambda *a, **k: (self.calls.__setitem__(name, self.calls[name] + 1),
+                                                                   f(*a, **k))[1])(n, fn))
+        return self.calls
+
+    def __exit__(self, *exc):
+        for n in self.NAMES:
+            delattr(self.kp, n)
+        return False
+
+
+def _fused_step(monkeypatch, zd, td, OH, OW, ignore, thresh, min_kept, w):
+    """criterion(DeferredUpsample(z)) with the switch on -> (loss, sel, dz); asserts that the fused kernels ran"""
+    from torchseg_amd import losses
+    from torchseg_amd.upsample import DeferredUpsample
+    monkeypatch.setattr(losses, "FUSE_HEAD_WIDE", True)
+    za = zd.clone().requires_grad_(True)
+    with _Spy() as calls:
+        loss, sel = losses.ohem_cross_entropy(DeferredUpsample(za, (OH, OW)), td, ignore, thresh, min_kept, w,
+                                              return_selection=True)
+        loss.backward()
+    assert calls["ohem_up_fwd"] == 1 and calls["ohem_up_bwd"] == 1 and calls["upsample_fwd"] == 0, calls
+    return loss, sel.cpu(), za.grad
+
+
+def _check_vs_oracle(loss, sel, dz, ref_loss, info, gref, exact_kept):
+    assert int(sel[3]) == info["branch"]
+    assert int(sel[2]) == info["num_valid"]
+    print("loss %.7f (oracle %.7f)" % (loss.item(), ref_loss.item()))
+    assert abs(loss.item() - ref_loss.item()) <= 1e-4 * max(1.0, abs(ref_loss.item()))
+    near = 0
+    if not exact_kept and info["mask_prob"] is not None:      # membership may flip only within ~2 ulp of the threshold
+        near = int((np.abs(info["mask_prob"].numpy() - info["threshold"]) <= 4e-7 * info["threshold"]).sum())
+    assert near <= 16                                          # the allowance cannot hide a wrong selection
+    print("kept %d (oracle %d), near %d" % (int(sel[1]), info["n_kept"], near))
+    assert abs(int(sel[1]) - info["n_kept"]) <= near
+    gscale = gref.abs().max().item()
+    err = (dz.float().cpu() - gref).abs().max().item()
+    print("max |dz - ref| %.3e of %.3e" % (err, gscale))
+    assert err <= 2e-4 * gscale + (1e-3 * gscale if near else 0.0), (err, gscale, near)
+
+
+# ---- 1. plain CE (thresh 1.0, min_kept 0: branch 2) -----------------------------------------------------------------
+# uint8 labels cannot name 256 classes and an ignore value: that case runs with int64 labels only
+@pytest.mark.parametrize("case,kind", [(c, k) for c in PLAIN for k in ("u8", "i64") if not (c[1] > 255 and k == "u8")])
+def test_plain_ce_vs_oracle_fp32(cuda, monkeypatch, case, kind):
+    B, C, IH, IW, OH, OW, _ = case
+    z, t, _, ref_loss, info, gref = _oracle(case, 255, 1.0, 0)
+    if C == 256:
+        assert bool((t == 255).any()) and bool((t == 0).any())
+    assert info["branch"] == 2
+    loss, sel, dz = _fused_step(monkeypatch, z.to(cuda), _labels(t, kind, cuda), OH, OW, 255, 1.0, 0, None)
+    assert int(sel[1]) == int(sel[2]) == info["num_valid"] and int(sel[5]) == 0
+    _check_vs_oracle(loss, sel, dz, ref_loss, info, gref, exact_kept=True)
+
+
+def test_class_255_of_256_is_a_class_when_the_ignore_label_is_not_255(cuda, monkeypatch):
+    """C = 256 with ignore label -1 (int64 labels): 255 names a class, so the kernels' per-tile label bytes cannot use
+    it as their "takes no part" mark."""
+    case = PLAIN[4]
+    B, C, IH, IW, OH, OW, _ = case
+    z, t, _, ref_loss, info, gref = _oracle(case, -1, 1.0, 0, redraw=True)
+    assert bool((t == 255).any()) and bool((t == 0).any()) and bool((t == -1).any())
+    assert info["num_valid"] == int((t != -1).sum())
+    loss, sel, dz = _fused_step(monkeypatch, z.to(cuda), t.to(cuda), OH, OW, -1, 1.0, 0, None)
+    assert int(sel[1]) == int(sel[2]) == info["num_valid"] and int(sel[5]) == 0
+    _check_vs_oracle(loss, sel, dz, ref_loss, info, gref, exact_kept=True)
+
+
+# ---- 2. OHEM, both threshold branches --------------------------------------------------------------------------------
+OHEM = [  # case, min_kept fraction, thresh, branch
+    ((2, 150, 12, 10, 96, 80, "confident"), 1 / 3, 0.7, 0),
+    ((1, 40, 6, 6, 96, 96, "confident"), 1 / 4, 0.7, 0),
+    ((2, 150, 8, 8, 64, 64, "trained"), 1 / 4, 0.7, 1),
+]
+
+
+@pytest.mark.parametrize("case,frac,thresh,branch", OHEM)
+def test_ohem_vs_oracle_fp32(cuda, monkeypatch, case, frac, thresh, branch):
+    from torchseg_amd import kernels as K
+    B, C, IH, IW, OH, OW, _ = case
+    k = int(B * OH * OW * frac)
+    z, t, _, ref_loss, info, gref = _oracle(case, 255, thresh, k)
+    assert info["branch"] == branch
+    if branch == 1:                                  # the oracle's threshold is isolated (see _TRAINED_SEED)
+        assert int((np.abs(info["mask_prob"].numpy() - info["threshold"]) <= 2e-5 * info["threshold"]).sum()) == 1
+    zd, td = z.to(cuda), t.to(cuda)
+    loss, sel, dz = _fused_step(monkeypatch, zd, td, OH, OW, 255, thresh, k, None)
+    print("threshold %.9g (oracle %.9g)" % (sel[0:1].view(torch.float32).item(), info["threshold"]))
+    _check_vs_oracle(loss, sel, dz, ref_loss, info, gref, exact_kept=False)
+    # kernel level: the selection is bit-exact given the device's own probabilities
+    kp = K.provider()
+    assert kp.ohem_up_wide_supported(zd, OH, OW) and not kp.ohem_up_supported(zd, OH, OW, thresh)
+    loss_k, nll, lse, sel_k = kp.ohem_up_fwd(zd, td, OH, OW, 255, thresh, k, None)
+    sel_k = sel_k.cpu()
+    assert torch.equal(sel_k[:6], sel[:6]) and loss_k.item() == loss.item()
+    p_dev = kp.ohem_target_prob(nll, td, C, 255).cpu()
+    thr_dev = sel_k[0:1].view(torch.float32).item()
+    if branch == 1:
+        assert int(sel_k[0]) == torch.sort(p_dev)[0][k - 1].view(torch.int32).item()
+    else:
+        assert thr_dev == np.float32(thresh)
+    valid = t.view(-1) != 255
+    assert int(sel_k[1]) == int((valid & (p_dev <= thr_dev)).sum())
+    # the device's probabilities against the oracle's: the bound of test_benched_head_bf16_uint8_labels_vs_oracle, on which
+    # the isolation band of _TRAINED_SEED rests
+    mp = info["mask_prob"]
+    perr = ((p_dev - mp).abs()[valid] / mp[valid].clamp_min(1e-30)).max().item()
+    print("p_t relative error %.2e" % perr)
+    assert perr <= 2e-5, perr
+
+
+# ---- 3. class weights: the [C] weight table ---------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", ["u8", "i64"])
+def test_class_weights_vs_torch(cuda, monkeypatch, kind):
+    case = (2, 150, 9, 7, 36, 28, "confident")
+    B, C, IH, IW, OH, OW, _ = case
+    z, t, w, _, _, _ = _oracle(case, 255, 1.0, 0, wseed=3)
+    zr = z.clone().requires_grad_(True)
+    ref = F.cross_entropy(F.interpolate(zr, size=(OH, OW), mode="bilinear", align_corners=True), t, weight=w,
+                          ignore_index=255)
+    ref.backward()
+    loss, sel, dz = _fused_step(monkeypatch, z.to(cuda), _labels(t, kind, cuda), OH, OW, 255, 1.0, 0, w.to(cuda))
+    assert int(sel[3]) == 2 and int(sel[1]) == int(sel[2]) == int((t != 255).sum())
+    assert abs(loss.item() - ref.item()) <= 1e-4 * max(1.0, abs(ref.item())), (loss.item(), ref.item())
+    gscale = zr.grad.abs().max().item()
+    err = (dz.cpu() - zr.grad).abs().max().item()
+    assert err <= 2e-4 * gscale, (err, gscale)
+
+
+# ---- 4. bf16: fused against the materialised HIP path ----------------------------------------------------------------
+def test_fused_equals_materialised_hip_path_bf16(cuda, monkeypatch):
+    """the two bounds of test_fused_equals_unfused_hip_path for bf16"""
+    from torchseg_amd import losses
+    from torchseg_amd.upsample import upsample_bilinear_ac
+    case = (2, 150, 16, 16, 128, 128, "confident")
+    B, C, IH, IW, OH, OW, regime = case
+    z, t = _make(B, C, IH, IW, OH, OW, regime, seed=9)
+    k = B * OH * OW // 16
+    tol = 2e-2
+    zd = z.to(cuda).to(torch.bfloat16)
+    td = t.to(cuda)
+    la, _, ga = _fused_step(monkeypatch, zd, td, OH, OW, 255, 0.7, k, None)
+    zb = zd.clone().requires_grad_(True)
+    with _Spy() as calls:
+        lb = losses.ohem_cross_entropy(upsample_bilinear_ac(zb, size=(OH, OW)), td, 255, 0.7, k)
+        lb.backward()
+    assert calls["ohem_up_fwd"] == 0 and calls["ohem_fwd"] == 1, calls
+    print("bf16 loss fused %.6f materialised %.6f" % (la.item(), lb.item()))
+    assert abs(la.item() - lb.item()) <= max(tol, 1e-5) * max(1.0, abs(lb.item())) * 50
+    scale = zb.grad.float().abs().max().item()
+    err = (ga.float() - zb.grad.float()).abs().max().item()
+    print("bf16 max |dz fused - materialised| %.3e of %.3e" % (err, scale))
+    assert err <= (tol * 5) * scale
+
+
+# ---- 5. / 6. bit-equal repeats; poisoned, guard-banded buffers ---------------------------------------------------------
+def _kernel_calls(kp, z, t, OH, OW, k, gs):
+    loss, nll, lse, sel = kp.ohem_up_fwd(z, t, OH, OW, 255, 0.7, k, None)
+    dz = kp.ohem_up_bwd(z, t, OH, OW, 255, None, nll, lse, sel, gs)
+    return loss, nll, lse, sel[:6], dz            # sel[6:] is not part of the result
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_two_runs_are_bit_equal(cuda, dtype):
+    from torchseg_amd import kernels as K
+    kp = K.provider()
+    B, C, IH, IW, OH, OW = 2, 150, 12, 10, 96, 80
+    z, t = _make(B, C, IH, IW, OH, OW, "confident", seed=4)
+    zd, td = z.to(cuda).to(dtype), t.to(torch.uint8).to(cuda)
+    gs = torch.full((1,), 0.75, device=cuda)
+    runs = [_kernel_calls(kp, zd, td, OH, OW, B * OH * OW // 3, gs) for _ in range(2)]
+    _guard.assert_bit_identical(runs, ["first", "second"])
+    assert runs[0][4].dtype == dtype and bool(torch.isfinite(runs[0][4].float()).all()) and float(runs[0][4].float().abs().max()) > 0
+
+
+@pytest.mark.parametrize("shape", [(2, 150, 9, 7, 36, 28), (1, 33, 8, 8, 64, 64)])
+def test_under_guard_bands(cuda, shape):
+    from torchseg_amd import kernels as K
+    kp = K.provider()
+    B, C, IH, IW, OH, OW = shape
+    z, t = _make(B, C, IH, IW, OH, OW, "confident", seed=6)
+    zd, td = z.to(cuda), t.to(cuda)
+    gs = torch.full((1,), 1.25, device=cuda)
+    k = B * OH * OW // 3
+    results, names = [_kernel_calls(kp, zd, td, OH, OW, k, gs)], ["plain"]
+    for fill in _guard.FILLS:
+        with _guard.Guarded(fill) as g:
+            out = _kernel_calls(kp, g.guarded(zd), g.guarded(td), OH, OW, k, g.guarded(gs))
+        g.check()
+        results.append(out)
+        names.append("guarded 0x%02X" % fill)
+    _guard.assert_bit_identical(results, names)
+    assert bool(torch.isfinite(results[0][4]).all()) and bool(torch.isfinite(results[0][2]).all())
+
+
+# ---- 7. routing ----------------------------------------------------------------------------------------------------------
+def test_routing_follows_the_switch(cuda, monkeypatch):
+    from torchseg_amd import kernels as K, losses
+    from torchseg_amd.upsample import DeferredUpsample
+    kp = K.provider()
+    z, t = _make(2, 150, 8, 8, 64, 64, "random", seed=2)
+    zd, td = z.to(cuda), t.to(cuda)
+    for on in (True, False):
+        monkeypatch.setattr(losses, "FUSE_HEAD_WIDE", on)
+        za = zd.clone().requires_grad_(True)
+        with _Spy() as calls:
+            losses.cross_entropy_2d(DeferredUpsample(za, (64, 64)), td, ignore_index=255).backward()
+        if on:
+            assert calls == dict(ohem_up_fwd=1, ohem_up_bwd=1, upsample_fwd=0, upsample_bwd=0, ohem_fwd=0, ohem_bwd=0), calls
+        else:
+            assert calls["ohem_up_fwd"] == 0 and calls["ohem_up_bwd"] == 0, calls
+            assert calls["upsample_fwd"] == 1 and calls["ohem_fwd"] == 1 and calls["ohem_bwd"] == 1, calls
+        assert not kp.ohem_up_supported(zd, 64, 64, 1.0)              # the narrow query never takes C > 32
+        assert za.grad is not None
+
+
+class _Head(nn.Module):
+    """pspnet network.py:46-56 in a test-authored module: 1x1 classifier, x8 bilinear, log_softmax, CrossEntropyLoss"""
+
+    def __init__(self):
+        super().__init__()
+        self.conv = nn.Conv2d(16, 150, 1)
+        self.criterion = nn.CrossEntropyLoss(reduction='mean', ignore_index=255)
+
+    def forward(self, x, label):
+        fm = F.interpolate(self.conv(x), scale_factor=8, mode='bilinear', align_corners=True)
+        return self.criterion(F.log_softmax(fm, dim=1), label)
+
+
+def test_pspnet_statements_reach_the_fused_call_under_fusemode(cuda, monkeypatch):
+    from torchseg_amd import losses
+    from torchseg_amd.fusion import FuseMode
+    monkeypatch.setattr(losses, "FUSE_HEAD_WIDE", True)
+    torch.manual_seed(8)
+    head = _Head().to(cuda)
+    g = torch.Generator().manual_seed(8)
+    x = torch.randn(2, 16, 9, 11, generator=g)
+    label = torch.randint(0, 150, (2, 72, 88), generator=g)
+    label[:, :5] = 255
+    label = label.to(cuda)
+    xr = x.to(cuda).requires_grad_(True)
+    ref = head(xr, label)
+    ref.backward()
+    xf = x.to(cuda).requires_grad_(True)
+    with _Spy() as calls:
+        with FuseMode(head=True, loss=True):
+            out = head(xf, label)
+        out.backward()
+    assert calls["ohem_up_fwd"] == 1 and calls["ohem_up_bwd"] == 1 and calls["upsample_fwd"] == 0 and calls["ohem_fwd"] == 0, calls
+    assert abs(out.item() - ref.item()) <= 1e-4 * max(1.0, abs(ref.item())), (out.item(), ref.item())
+    scale = xr.grad.abs().max().item()
+    assert (xf.grad - xr.grad).abs().max().item() <= 2e-4 * scale

@@ -1086,6 +1086,367 @@ __global__ __launch_bounds__(NTMAX) void ohem_up_bwd_k(
   if (cur >= 0) { flush(cur, accA); flush(cur + 1, accB); }
 }
 
+// =============================================================================
+// Fused head for 33 <= C <= 256 classes (ADE20K: 150).  The narrow kernels above keep every class of a pixel in
+// registers; here the classes are walked in chunks of CP.
+//   forward : the same 256 x 32 tile.  Per chunk the z window of CP classes is staged in LDS (pixel-major, as in
+//             ohem_up_fwd2_k) and every row of the tile folds the chunk into an ONLINE softmax state held in registers
+//             per row: running maximum m[r] and sum s[r] of exp2(logit - m[r]), rescaled when the maximum moves: exact,
+//             no underflow case.  The target logit is taken from the window of the chunk that holds the target class,
+//             with the expressions that produce v[t].  The row loop is unrolled (the state is indexed by the row).
+//             Labels sit in LDS as 16-bit values (0xffff = takes no part): class 255 is a class when C = 256.
+//   backward: with lse saved the classes are independent, g_c = coef * (exp2(v_c - lse2) - [c == t]): ohem_up_bwd_k's
+//             structure per class chunk, the chunk being part of blockIdx.z.  z / dz are indexed with the full C stride;
+//             the one-hot row is t - c0 inside the chunk and a row of zeros otherwise.  One owner per dz element.
+// =============================================================================
+constexpr int kWideMaxC = 256;
+constexpr int kLabNone = 0xffff;
+
+template <typename T, int LT, int CP>
+__global__ __launch_bounds__(kT) void ohem_upw_fwd_k(
+    const T* __restrict__ z, const void* __restrict__ labels, int64_t B, UpFwdGeom g,
+    int64_t ignore_label, float thresh, int64_t tb, int shift0, int bins0,
+    const float* __restrict__ weight, float* __restrict__ nll_out, float* __restrict__ lse_out,
+    uint32_t* __restrict__ hist0, BlkPart* __restrict__ part) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lh[];       // [hist_words] histogram
+  const int C = g.C, IH = g.IH, IW = g.IW, OH = g.OH, OW = g.OW, WR = g.WR, WC = g.WC;
+  const int npix = WR * WC;
+  float* Zw = reinterpret_cast<float*>(lh + g.hist_words);            // [npix][CP] window of one class chunk of z * log2(e)
+  int* yro = reinterpret_cast<int*>(Zw + (size_t)npix * CP);          // [kFwdBand] window pixel offset of the row's y0
+  float* yly = reinterpret_cast<float*>(yro + kFwdBand);              // [kFwdBand] lambda_y of the row
+  float* wtab = yly + kFwdBand;                                       // [kWideMaxC] class weights (1 without a weight vector)
+  uint16_t* lab_s = reinterpret_cast<uint16_t*>(wtab + kWideMaxC);    // [kFwdBand][kT] labels (kLabNone = takes no part)
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  for (int i = tid; i < bins0; i += kT) lh[i] = 0;
+  for (int i = tid; i < kWideMaxC; i += kT) wtab[i] = (weight && i < C) ? weight[i] : 1.f;
+  PassAcc acc;
+  const int64_t total = B * g.bands * (int64_t)g.xblocks;
+  const int64_t plane = (int64_t)IH * IW;
+  for (int64_t tile = blockIdx.x; tile < total; tile += gridDim.x) {
+    const int xb = (int)(tile % g.xblocks);
+    const int band = (int)((tile / g.xblocks) % g.bands);
+    const int64_t b = tile / ((int64_t)g.xblocks * g.bands);
+    const int oy_beg = band * kFwdBand;
+    const int oy_end = oy_beg + kFwdBand < OH ? oy_beg + kFwdBand : OH;
+    const int ox = xb * kT + tid;
+    const bool live = ox < OW;
+    int ys_lo, xs_lo, t1; float tf;
+    src_index0(g.sy, oy_beg, IH, ys_lo, t1, tf);
+    src_index0(g.sx, xb * kT, IW, xs_lo, t1, tf);
+    const T* zb = z + b * C * plane;
+    __syncthreads();                                   // the previous tile's readers are done (also orders lh / wtab init)
+    if (tid < kFwdBand) {
+      int y0, y1; float ly;
+      const int oy = oy_beg + tid < OH ? oy_beg + tid : OH - 1;
+      src_index0(g.sy, oy, IH, y0, y1, ly);
+      yro[tid] = (y0 - ys_lo) * WC;
+      yly[tid] = ly;
+    }
+#pragma unroll 1
+    for (int u0 = 0; u0 < kFwdBand; u0 += 16) {
+      int64_t lab[16];
+      const int oxc = ox < OW ? ox : OW - 1;
+#pragma unroll
+      for (int u = 0; u < 16; ++u) {
+        const int oy = oy_beg + u0 + u;
+        const int oyc = oy < OH ? oy : OH - 1;
+        const int64_t v = Lab<LT>::get(labels, (b * OH + oyc) * (int64_t)OW + oxc);     // unconditional, clamped
+        lab[u] = (live && oy < oy_end) ? v : ignore_label;
+      }
+#pragma unroll
+      for (int u = 0; u < 16; ++u) {
+        const bool is_cls = label_is_class(lab[u], ignore_label, C);
+        if (!is_cls && lab[u] != ignore_label) acc.cnt_bad++;
+        lab_s[(u0 + u) * kT + tid] = is_cls ? (uint16_t)lab[u] : (uint16_t)kLabNone;
+      }
+    }
+    int x0, x1; float lx;
+    src_index0(g.sx, live ? ox : OW - 1, IW, x0, x1, lx);
+    const int xl0 = x0 - xs_lo;                        // x1 = x0 + 1 except on the last source column, where lx = 0 and the
+    //                                                    window's clamped copy of that column sits at xl0 + 1
+    const up_f2 lx2 = {lx, lx};
+    const int nrows = oy_end - oy_beg;
+    float m[kFwdBand], s[kFwdBand], xt[kFwdBand];      // per row: running maximum, sum of exp2(logit - m), target logit
+#pragma unroll
+    for (int r = 0; r < kFwdBand; ++r) { m[r] = kNegBig; s[r] = 0.f; xt[r] = 0.f; }
+#pragma unroll 1
+    for (int c0 = 0; c0 < C; c0 += CP) {
+      if (c0) __syncthreads();                         // the previous chunk's readers are done
+      // window of classes [c0, c0 + CP): wave wv takes the (class, row) pairs wv, wv + 4, ...; lanes = source columns;
+      // eight pairs' loads in flight per wave, unconditional from clamped addresses (see ohem_up_fwd2_k)
+      for (int x0s = 0; x0s < WC; x0s += 64) {
+        const int xx = x0s + lane;
+        const int xg = xs_lo + xx < IW ? xs_lo + xx : IW - 1;
+        const bool xin = xx < WC;
+        int c = 0, rr = wv;
+        while (rr >= WR) { rr -= WR; ++c; }
+        while (c < CP) {
+          float val[8];
+          int off[8];
+#pragma unroll
+          for (int u = 0; u < 8; ++u) {
+            const bool on = c < CP;
+            const int yy = ys_lo + rr < IH ? ys_lo + rr : IH - 1;
+            const int cg = c0 + c;
+            const int cc = cg < C ? cg : C - 1;
+            const float raw = ld1<T>(zb + (int64_t)cc * plane + (int64_t)yy * IW + xg) * kLog2e;
+            val[u] = cg < C ? raw : kNegBig;
+            off[u] = (on && xin) ? (rr * WC + xx) * CP + c : -1;
+            rr += kT / 64;
+            while (rr >= WR) { rr -= WR; ++c; }
+          }
+#pragma unroll
+          for (int u = 0; u < 8; ++u)
+            if (off[u] >= 0) Zw[off[u]] = val[u];
+        }
+      }
+      __syncthreads();
+      if (live) {
+        up_f2 H0[CP / 2], D[CP / 2];
+        int cro = -1, p00 = 0;
+#pragma unroll
+        for (int r = 0; r < kFwdBand; ++r) {
+          if (r < nrows) {
+            const int ro = __builtin_amdgcn_readfirstlane(yro[r]);
+            const float ly = yly[r];
+            if (ro != cro) {
+              p00 = (ro + xl0) * CP;
+              const float4* A0 = reinterpret_cast<const float4*>(Zw + p00);
+              const float4* A1 = reinterpret_cast<const float4*>(Zw + p00 + CP);
+              const float4* B0 = reinterpret_cast<const float4*>(Zw + p00 + WC * CP);
+              const float4* B1 = reinterpret_cast<const float4*>(Zw + p00 + WC * CP + CP);
+#pragma unroll
+              for (int q = 0; q < CP / 4; ++q) {
+                const float4 a0 = A0[q], a1 = A1[q], b0 = B0[q], b1 = B1[q];
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                  const up_f2 a0p = k ? up_f2{a0.z, a0.w} : up_f2{a0.x, a0.y};
+                  const up_f2 a1p = k ? up_f2{a1.z, a1.w} : up_f2{a1.x, a1.y};
+                  const up_f2 b0p = k ? up_f2{b0.z, b0.w} : up_f2{b0.x, b0.y};
+                  const up_f2 b1p = k ? up_f2{b1.z, b1.w} : up_f2{b1.x, b1.y};
+                  const up_f2 h0 = __builtin_elementwise_fma(lx2, a1p - a0p, a0p);
+                  const up_f2 h1 = __builtin_elementwise_fma(lx2, b1p - b0p, b0p);
+                  H0[q * 2 + k] = h0;
+                  D[q * 2 + k] = h1 - h0;
+                }
+              }
+              cro = ro;
+            }
+            up_f2 v[CP / 2];
+            const up_f2 ly2 = {ly, ly};
+            float mc = kNegBig;
+#pragma unroll
+            for (int c = 0; c < CP / 2; ++c) {
+              v[c] = __builtin_elementwise_fma(ly2, D[c], H0[c]);
+              mc = fmaxf(mc, fmaxf(v[c].x, v[c].y));
+            }
+            const float mn = fmaxf(m[r], mc);
+            const up_f2 mn2 = {mn, mn};
+            up_f2 s2 = {0.f, 0.f};
+#pragma unroll
+            for (int c = 0; c < CP / 2; ++c) {
+              const up_f2 d = v[c] - mn2;
+              s2 += up_f2{__builtin_amdgcn_exp2f(d.x), __builtin_amdgcn_exp2f(d.y)};
+            }
+            s[r] = __builtin_fmaf(s[r], __builtin_amdgcn_exp2f(m[r] - mn), s2.x + s2.y);
+            m[r] = mn;
+            // the target logit, by the expressions that produced v[t - c0], when this chunk holds the target class
+            const int tl = (int)lab_s[r * kT + tid] - c0;
+            const bool mine = (unsigned)tl < (unsigned)CP;
+            const int tt = mine ? tl : 0;
+            const float a0 = Zw[p00 + tt], a1 = Zw[p00 + CP + tt], b0 = Zw[p00 + WC * CP + tt], b1 = Zw[p00 + WC * CP + CP + tt];
+            const float h0 = __builtin_fmaf(lx, a1 - a0, a0), h1 = __builtin_fmaf(lx, b1 - b0, b0);
+            const float xv = __builtin_fmaf(ly, h1 - h0, h0);
+            xt[r] = mine ? xv : xt[r];
+          }
+        }
+      }
+    }
+    if (live) {
+      float* nll_p = nll_out + (b * OH + oy_beg) * (int64_t)OW + ox;
+      float* lse_p = lse_out + (b * OH + oy_beg) * (int64_t)OW + ox;
+#pragma unroll
+      for (int r = 0; r < kFwdBand; ++r) {
+        if (r < nrows) {
+          const float l2 = m[r] + __builtin_amdgcn_logf(s[r]);
+          const int lab = lab_s[r * kT + tid];
+          const bool valid = lab != kLabNone;
+          const int t = valid ? lab : 0;
+          float nl = (l2 - xt[r]) * kLn2;
+          nl = nl < 0.f ? 0.f : nl;
+          nl = valid ? nl : 0.f;
+          nll_p[(int64_t)r * OW] = nl;
+          lse_p[(int64_t)r * OW] = l2 * kLn2;
+          account(acc, valid, nl, wtab[t], thresh, tb, shift0, bins0, lh);
+        }
+      }
+    }
+  }
+  fold_block(acc, lh, bins0, hist0, part);
+}
+
+template <typename T, int LT, int CP, int NTMAX>
+__global__ __launch_bounds__(NTMAX) void ohem_upw_bwd_k(
+    const T* __restrict__ z, const void* __restrict__ labels, UpBwdGeom g, int nchunk, int64_t ignore_label,
+    const float* __restrict__ weight, const float* __restrict__ nll, const float* __restrict__ lse,
+    const int32_t* __restrict__ sel, const float* __restrict__ gscale, T* __restrict__ dz) {
+  constexpr int VP = CP + 1;                          // odd row stride, as in ohem_up_bwd_k
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int NT = blockDim.x, tid = threadIdx.x;
+  const int C = g.C, IH = g.IH, IW = g.IW, OH = g.OH, OW = g.OW, XS = g.XS;
+  float* oh = smem;                                   // [CP + 1][CP] one-hot rows; row CP (target outside the chunk) is zero
+  float* Zr = oh + (CP + 1) * CP;                     // [2][CP][XS] the two live source rows * log2(e)
+  float* lxs = Zr + 2 * CP * XS;                      // [NT] lambda_x of every column of the block
+  float* Vs = lxs + NT;                               // [NT][VP] a completed source row, before the horizontal taps
+  int* xst = reinterpret_cast<int*>(Vs + NT * VP);    // [XS + 2] first column whose x0 is xs_lo + j
+  float* wtab = reinterpret_cast<float*>(xst + XS + 2);   // [kWideMaxC] class weights
+  const int s0 = blockIdx.x * g.SB, s1 = s0 + g.SB < IW ? s0 + g.SB : IW;
+  const int r0 = blockIdx.y * g.RB, r1 = r0 + g.RB < IH ? r0 + g.RB : IH;
+  const int64_t b = blockIdx.z / nchunk;
+  const int c0 = (int)(blockIdx.z % nchunk) * CP;     // this block's classes: [c0, c0 + Cc)
+  const int Cc = C - c0 < CP ? C - c0 : CP;
+  int xlo, xhi, tmp;
+  footprint(g.sx, s0, OW, xlo, tmp);
+  footprint(g.sx, s1 - 1, OW, tmp, xhi);
+  const int nact = xhi - xlo + 1;                     // <= NT (host)
+  const bool live = tid < nact;
+  const int ox = live ? xlo + tid : xhi;
+  int x0, x1, xs_lo; float lx, tf;
+  src_index0(g.sx, ox, IW, x0, x1, lx);
+  src_index0(g.sx, xlo, IW, xs_lo, tmp, tf);
+  const int xl0 = x0 - xs_lo, xl1 = x1 - xs_lo;
+  lxs[tid] = live ? lx : 0.f;
+  for (int i = tid; i < (CP + 1) * CP; i += NT) oh[i] = (i / CP == i % CP) ? 1.f : 0.f;
+  for (int j = tid; j < XS + 2; j += NT) xst[j] = nact;
+  for (int i = tid; i < kWideMaxC; i += NT) wtab[i] = (weight && i < C) ? weight[i] : 1.f;
+  __syncthreads();
+  if (live) {
+    int p0 = -1, p1; float pf;
+    if (tid > 0) src_index0(g.sx, ox - 1, IW, p0, p1, pf);
+    if (p0 != x0) xst[xl0] = tid;                     // OW >= 2 IW: x0 advances by at most 1 per column
+  }
+  const float thr = __uint_as_float((uint32_t)sel[0]);
+  const int branch = sel[3];
+  const float gs = gscale[0] / reinterpret_cast<const float*>(sel)[4];
+  const int64_t plane = (int64_t)IH * IW;
+  const T* zb = z + (b * C + c0) * plane;
+  // output rows whose y0 lies in [r0-1, r1-1]
+  int oy_lo = 0, oy_hi = OH - 1;
+  if (g.sy > 0.f) {
+    const float inv = 1.f / g.sy;
+    const int l = (int)ceilf((float)(r0 - 1) * inv) - 1;
+    const int h = (int)floorf((float)r1 * inv) + 1;
+    oy_lo = l < 0 ? 0 : l;
+    oy_hi = h > OH - 1 ? OH - 1 : h;
+  }
+  up_f2 H0[CP / 2], D[CP / 2], accA[CP / 2], accB[CP / 2];
+#pragma unroll
+  for (int c = 0; c < CP / 2; ++c) { accA[c] = up_f2{0.f, 0.f}; accB[c] = up_f2{0.f, 0.f}; H0[c] = up_f2{0.f, 0.f}; D[c] = up_f2{0.f, 0.f}; }
+  int cur = -2;                                       // source row accA belongs to (accB: cur + 1)
+  int staged0 = -1, staged1 = -1;                     // source rows held by the two ring slots
+
+  auto flush = [&](int row, const up_f2 (&a)[CP / 2]) {   // block-uniform
+    if (row < r0 || row >= r1) return;
+    __syncthreads();                                  // the previous horizontal pass has read Vs
+#pragma unroll
+    for (int c = 0; c < CP / 2; ++c) {
+      Vs[tid * VP + 2 * c] = live ? a[c].x : 0.f;
+      Vs[tid * VP + 2 * c + 1] = live ? a[c].y : 0.f;
+    }
+    __syncthreads();
+    const int nS = s1 - s0;
+    for (int idx = tid; idx < Cc * nS; idx += NT) {
+      const int c = idx % Cc, s = s0 + idx / Cc, j = s - xs_lo;
+      float sum = 0.f;
+      const int xa = xst[j], xb = xst[j + 1];
+      for (int x = xa; x < xb; ++x) sum = __builtin_fmaf(1.f - lxs[x], Vs[x * VP + c], sum);
+      if (j >= 1) {
+        const int xp = xst[j - 1];
+        for (int x = xp; x < xa; ++x) sum = __builtin_fmaf(lxs[x], Vs[x * VP + c], sum);
+      }
+      st1<T>(dz + ((b * C + c0 + c) * IH + row) * (int64_t)IW + s, sum);
+    }
+  };
+  auto stage = [&](int slot, int y) {
+    for (int i = tid; i < CP * XS; i += NT) {
+      const int c = i / XS, xx = i % XS;
+      const int xg = xs_lo + xx < IW ? xs_lo + xx : IW - 1;
+      Zr[slot * CP * XS + i] = c < Cc ? ld1<T>(zb + c * plane + (int64_t)y * IW + xg) * kLog2e : kNegBig;
+    }
+  };
+  struct Side { typename Lab<LT>::raw_t lab; float nl, ls; };
+  auto load_side = [&](int oy) {                      // unconditional, untouched until used: see ohem_up_bwd_k
+    Side sd;
+    const int64_t gp = (b * OH + oy) * (int64_t)OW + ox;
+    sd.lab = Lab<LT>::get_raw(labels, gp);
+    sd.nl = nll[gp];
+    sd.ls = lse[gp];
+    return sd;
+  };
+  Side nxt = load_side(oy_lo);
+  for (int oy = oy_lo; oy <= oy_hi; ++oy) {
+    const Side sd = nxt;
+    if (oy < oy_hi) nxt = load_side(oy + 1);
+    int y0, y1; float ly;
+    src_index0(g.sy, oy, IH, y0, y1, ly);
+    y0 = __builtin_amdgcn_readfirstlane(y0);
+    y1 = __builtin_amdgcn_readfirstlane(y1);
+    if (y0 < r0 - 1 || y0 > r1 - 1) continue;
+    if (y0 != cur) {
+      if (cur >= 0) {
+        flush(cur, accA);
+        if (y0 == cur + 1) {
+#pragma unroll
+          for (int c = 0; c < CP / 2; ++c) { accA[c] = accB[c]; accB[c] = up_f2{0.f, 0.f}; }
+        } else {
+          flush(cur + 1, accB);
+#pragma unroll
+          for (int c = 0; c < CP / 2; ++c) { accA[c] = up_f2{0.f, 0.f}; accB[c] = up_f2{0.f, 0.f}; }
+        }
+      }
+      __syncthreads();                                // everybody has built H0 / D from the rows about to be replaced
+      if (((y0 & 1) ? staged1 : staged0) != y0) { stage(y0 & 1, y0); if (y0 & 1) staged1 = y0; else staged0 = y0; }
+      if (y1 != y0 && ((y1 & 1) ? staged1 : staged0) != y1) { stage(y1 & 1, y1); if (y1 & 1) staged1 = y1; else staged0 = y1; }
+      __syncthreads();
+      const float* za = Zr + (y0 & 1) * CP * XS;
+      const float* zc = Zr + (y1 & 1) * CP * XS;
+#pragma unroll
+      for (int c = 0; c < CP; ++c) {
+        const float a0 = za[c * XS + xl0], a1 = za[c * XS + xl1], b0 = zc[c * XS + xl0], b1 = zc[c * XS + xl1];
+        const float h0 = __builtin_fmaf(lx, a1 - a0, a0), h1 = __builtin_fmaf(lx, b1 - b0, b0);
+        if (c & 1) { H0[c >> 1].y = h0; D[c >> 1].y = h1 - h0; } else { H0[c >> 1].x = h0; D[c >> 1].x = h1 - h0; }
+      }
+      cur = y0;
+    }
+    const int64_t lab = Lab<LT>::widen(sd.lab);
+    const bool valid = live && label_is_class(lab, ignore_label, C);
+    bool kept = valid;
+    if (valid && branch != 2) kept = prob_of_nll(sd.nl) <= thr;
+    const int t = valid ? (int)lab : 0;
+    const float coef = kept ? gs * wtab[t] : 0.f;
+    if (__builtin_amdgcn_ballot_w64(coef != 0.f) == 0) continue;      // nothing kept in this wave's 64 columns
+    const float l2 = sd.ls * kLog2e;
+    const float ca = coef - ly * coef, cb = ly * coef;
+    const int tl = t - c0;
+    const float4* ohr = reinterpret_cast<const float4*>(oh + ((valid && (unsigned)tl < (unsigned)CP) ? tl : CP) * CP);
+    const up_f2 ly2 = {ly, ly}, l22 = {l2, l2}, ca2 = {ca, ca}, cb2 = {cb, cb};
+#pragma unroll
+    for (int c4 = 0; c4 < CP / 4; ++c4) {
+      const float4 o = ohr[c4];
+      const up_f2 ov[2] = {up_f2{o.x, o.y}, up_f2{o.z, o.w}};
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const int c = c4 * 2 + k;
+        const up_f2 v = __builtin_elementwise_fma(ly2, D[c], H0[c]) - l22;
+        const up_f2 e = up_f2{__builtin_amdgcn_exp2f(v.x), __builtin_amdgcn_exp2f(v.y)} - ov[k];
+        accA[c] = __builtin_elementwise_fma(ca2, e, accA[c]);
+        accB[c] = __builtin_elementwise_fma(cb2, e, accB[c]);
+      }
+    }
+  }
+  if (cur >= 0) { flush(cur, accA); flush(cur + 1, accB); }
+}
+
 static int up_class_pad(int C) { return C <= 8 ? 8 : C <= 16 ? 16 : C <= 20 ? 20 : C <= 24 ? 24 : 32; }
 // 4 register arrays of CP floats per thread.  TSG_HEAD_BWD_NT=512|1024: threads (= output columns) per backward block
 static int up_bwd_ntmax(int CP) {
@@ -1159,6 +1520,31 @@ static bool up_fused_ok(int C, int IH, int IW, int OH, int OW) {
   return up_bwd_cfg(1, C, IH, IW, OH, OW).ok;
 }
 
+// ---- wide (33..256 classes) -----------------------------------------------------
+constexpr int kWideBwdCP = 32;
+static size_t upw_fwd_lds(const UpFwdGeom& g, int CP) {
+  return (size_t)g.hist_words * 4 + (size_t)CP * g.WR * g.WC * 4 + (size_t)kFwdBand * 8 + (size_t)kWideMaxC * 4 +
+         (size_t)kFwdBand * kT * 2;
+}
+// the forward's class chunk: the largest whose window leaves room for two blocks per CU (0: none does)
+static int upw_fwd_cp(int C, int IH, int IW, int OH, int OW) {
+  const UpFwdGeom g = up_fwd_geom(C, IH, IW, OH, OW, 2048);
+  if (upw_fwd_lds(g, 32) <= 64 * 1024) return 32;
+  if (upw_fwd_lds(g, 16) <= 64 * 1024) return 16;
+  return 0;
+}
+// ohem_upw_bwd_k's LDS: up_bwd_cfg's figure + the zero one-hot row + a weight table of kWideMaxC instead of CP entries
+static size_t upw_bwd_lds(const UpBwdCfg& cf) { return cf.lds + (size_t)kWideMaxC * 4; }
+
+static bool up_wide_ok(int C, int IH, int IW, int OH, int OW) {
+  if (C <= 32 || C > kWideMaxC) return false;
+  if (IH < 1 || IW < 1 || OH < 2 * IH || OW < 2 * IW) return false;   // only genuine up-sampling is fused
+  const float sx = ac_scale(IW, OW), sy = ac_scale(IH, OH);
+  if (sx <= 0.f || sy <= 0.f || sx > 0.5f || sy > 0.5f) return false;
+  if (upw_fwd_cp(C, IH, IW, OH, OW) == 0) return false;
+  return up_bwd_cfg(1, C, IH, IW, OH, OW).ok;
+}
+
 static int pixel_grid(int64_t nvec) {
   int64_t g = (nvec + kT - 1) / kT;
   if (g > 4096) g = 4096;
@@ -1226,6 +1612,26 @@ static int launch_up_bwd(const UpBwdCfg& cf, int64_t B, const void* z, const voi
   }
   dim3 grid((unsigned)cf.k, (unsigned)((cf.g.IH + cf.g.RB - 1) / cf.g.RB), (unsigned)B);
   hipLaunchKernelGGL((ohem_up_bwd_k<T, LT, CP, NTMAX>), grid, dim3(cf.NT), cf.lds, st, (const T*)z, labels, cf.g,
+                     ignore_label, weight, nll, lse, sel, gscale, (T*)dz);
+  TSG_CHECK_LAUNCH();
+  return 0;
+}
+
+template <typename T, int LT, int CP, int NTMAX>
+static int launch_upw_bwd(const UpBwdCfg& cf, int64_t B, const void* z, const void* labels, int64_t ignore_label,
+                          const float* weight, const float* nll, const float* lse, const int32_t* sel,
+                          const float* gscale, void* dz, hipStream_t st) {
+  static size_t granted = 0;                            // dynamic LDS above 64 KB has to be requested once
+  const size_t lds = upw_bwd_lds(cf);
+  if (lds > 64 * 1024 && lds > granted) {
+    TSG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ohem_upw_bwd_k<T, LT, CP, NTMAX>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    granted = lds;
+  }
+  const int nchunk = (cf.g.C + CP - 1) / CP;
+  if (B * nchunk > 65535) return TSG_E_SHAPE;
+  dim3 grid((unsigned)cf.k, (unsigned)((cf.g.IH + cf.g.RB - 1) / cf.g.RB), (unsigned)(B * nchunk));
+  hipLaunchKernelGGL((ohem_upw_bwd_k<T, LT, CP, NTMAX>), grid, dim3(cf.NT), lds, st, (const T*)z, labels, cf.g, nchunk,
                      ignore_label, weight, nll, lse, sel, gscale, (T*)dz);
   TSG_CHECK_LAUNCH();
   return 0;
@@ -1327,6 +1733,10 @@ int tsg_ohem_up_supported(int C, int IH, int IW, int OH, int OW, float thresh) {
   return up_fused_ok(C, IH, IW, OH, OW) ? 1 : 0;
 }
 
+int tsg_ohem_up_wide_supported(int C, int IH, int IW, int OH, int OW) {
+  return up_wide_ok(C, IH, IW, OH, OW) ? 1 : 0;
+}
+
 size_t tsg_ohem_up_bwd_ws_bytes(int64_t B, int C, int IH, int OW) {
   if (B <= 0 || C <= 0 || IH <= 0 || OW <= 0) return 0;
   return 256;                                          // the backward needs no scratch any more; kept for the ABI
@@ -1339,7 +1749,8 @@ int tsg_ohem_up_fwd(const void* z, int dtype, const void* labels, int ltype, int
   if (!z || !labels || !nll || !lse || !loss || !sel || !ws) return TSG_E_NULL;
   if (dtype != TSG_F32 && dtype != TSG_BF16) return TSG_E_DTYPE;
   if (ltype != TSG_I64 && ltype != TSG_U8) return TSG_E_DTYPE;
-  if (IH <= 0 || IW <= 0 || !up_fused_ok(C, IH, IW, OH, OW)) return TSG_E_SHAPE;
+  const bool wide = C > 32;
+  if (IH <= 0 || IW <= 0 || !(wide ? up_wide_ok(C, IH, IW, OH, OW) : up_fused_ok(C, IH, IW, OH, OW))) return TSG_E_SHAPE;
   tsg_ohem_plan pl;
   int e = tsg_ohem_make_plan(B, C, (int64_t)OH * OW, thresh, &pl);
   if (e) return e;
@@ -1351,6 +1762,20 @@ int tsg_ohem_up_fwd(const void* z, int dtype, const void* labels, int ltype, int
   TSG_HIP(hipMemsetAsync(ws, 0, w.zero_bytes, st));
   const int64_t tb = thresh_tb(thresh);
   const UpFwdGeom g = up_fwd_geom(C, IH, IW, OH, OW, bins0);
+  if (wide) {
+    if (B * ((C + kWideBwdCP - 1) / kWideBwdCP) > 65535) return TSG_E_SHAPE;   // the backward's grid.z: refuse here, not after the forward
+    const int WCP = upw_fwd_cp(C, IH, IW, OH, OW);
+    const size_t wsh = upw_fwd_lds(g, WCP);
+#define PW(T, LTT, CM) hipLaunchKernelGGL((ohem_upw_fwd_k<T, LTT, CM>), dim3(pl.grid), dim3(kT), wsh, st, (const T*)z, labels, B, g, \
+                     ignore_label, thresh, tb, pl.shift[0], bins0, weight, nll, lse, w.hist[0], w.part)
+#define PWC(T, LTT) do { if (WCP == 32) PW(T, LTT, 32); else PW(T, LTT, 16); } while (0)
+    if (dtype == TSG_F32) { if (ltype == TSG_I64) PWC(float, TSG_I64); else PWC(float, TSG_U8); }
+    else { if (ltype == TSG_I64) PWC(bf16_t, TSG_I64); else PWC(bf16_t, TSG_U8); }
+#undef PWC
+#undef PW
+    TSG_CHECK_LAUNCH();
+    return ohem_select_tail(pl, w, labels, ltype, ignore_label, thresh, min_kept, weight, nll, loss, sel, tb, st);
+  }
   const int CP = up_class_pad(C);
   const size_t sh = up_fwd_lds(g, CP);
   const bool form2 = up_fwd_form() == 2;
@@ -1377,10 +1802,17 @@ int tsg_ohem_up_bwd(const void* z, int dtype, const void* labels, int ltype, int
   if (!z || !labels || !nll || !lse || !sel || !gscale || !dz) return TSG_E_NULL;
   if (dtype != TSG_F32 && dtype != TSG_BF16) return TSG_E_DTYPE;
   if (ltype != TSG_I64 && ltype != TSG_U8) return TSG_E_DTYPE;
-  if (B <= 0 || !up_fused_ok(C, IH, IW, OH, OW)) return TSG_E_SHAPE;
+  const bool wide = C > 32;
+  if (B <= 0 || !(wide ? up_wide_ok(C, IH, IW, OH, OW) : up_fused_ok(C, IH, IW, OH, OW))) return TSG_E_SHAPE;
   hipStream_t st = (hipStream_t)stream;
-  const UpBwdCfg cf = up_bwd_cfg(B, C, IH, IW, OH, OW);
+  const UpBwdCfg cf = up_bwd_cfg(wide ? B * ((C + kWideBwdCP - 1) / kWideBwdCP) : B, C, IH, IW, OH, OW);
   if (!cf.ok) return TSG_E_SHAPE;
+  if (wide) {
+#define PW(T, LTT) return launch_upw_bwd<T, LTT, kWideBwdCP, 512>(cf, B, z, labels, ignore_label, weight, nll, lse, sel, gscale, dz, st)
+    if (dtype == TSG_F32) { if (ltype == TSG_I64) PW(float, TSG_I64); else PW(float, TSG_U8); }
+    else { if (ltype == TSG_I64) PW(bf16_t, TSG_I64); else PW(bf16_t, TSG_U8); }
+#undef PW
+  }
 #define PB(T, LTT, CM, NM) return launch_up_bwd<T, LTT, CM, NM>(cf, B, z, labels, ignore_label, weight, nll, lse, sel, gscale, dz, st)
 #define PC(T, LTT) do { switch (up_class_pad(C)) { case 8: PB(T, LTT, 8, 1024); case 16: PB(T, LTT, 16, 1024); \
     case 20: PB(T, LTT, 20, 1024); case 24: PB(T, LTT, 24, 512); default: PB(T, LTT, 32, 512); } } while (0)

@@ -50,6 +50,9 @@ upsample overrides.  Controlled by env so train.py needs no edit:
   TSG_FUSE_HEAD=1|0     (default 1 on GPU: a bilinear F.interpolate of <= 32-channel logits by >= 4 stays pending and is
                         evaluated inside the criterion's kernels, tsg_ohem_up_*: 3x faster than writing and re-reading
                         the full-resolution logits; any other consumer materialises it.  fusion.py)
+  TSG_FUSE_HEAD_WIDE=0|1 (default 0: with TSG_FUSE_HEAD, heads of 33..256 classes (PSPNet / PSANet on ADE20K: 150) stay
+                        pending as well and run on the class-chunked fused kernels, tsg_ohem_up_wide_supported; losses.py,
+                        DESIGN.md 7)
   TSG_FUSE_CHAIN=1|0    (default 1 on GPU: a ConvBnRelu called right after another one (bisenet network.py:131-137) applies
                         the first one's BatchNorm + ReLU while its own convolution loads its input; fusion.PendingCbr)
   TSG_SPLIT_BIAS=1|0    (default 1 on GPU: conv bias add / bias grad through our column-sum kernel)

@@ -440,9 +440,21 @@ def _ce_args(args, kwargs):
     return x, tgt, w, int(a.get("ignore_index", -100))
 
 
+_LOSSES = None
+
+
+def _losses_module():
+    """torchseg_amd.losses, imported once on first use (losses imports this module)"""
+    global _LOSSES
+    if _LOSSES is None:
+        from . import losses
+        _LOSSES = losses
+    return _LOSSES
+
+
 class FuseMode(TorchFunctionMode):
     """See the module docstring.  `psa`: defer column softmaxes for the PSA contraction; `loss`: plain CE heads on
-    the HIP kernels; `add_up`: `+=` -> interpolate fusion; `head`: bilinear up-sampling of <= 32-channel logits by >= 4 is
+    the HIP kernels; `add_up`: `+=` -> interpolate fusion; `head`: bilinear up-sampling of <= 32-channel logits (<= 256 with losses.FUSE_HEAD_WIDE) by >= 4 is
     left pending for the criterion (fused upsample + CE / OHEM kernels); `chain`: consecutive ConvBnRelu modules hand
     their BatchNorm + ReLU to the next convolution (PendingCbr).
 
@@ -617,7 +629,7 @@ class FuseMode(TorchFunctionMode):
             x = args[0]
             OH, OW = _out_size(x, kwargs.get("size", args[1] if len(args) > 1 else None),
                                kwargs.get("scale_factor", args[2] if len(args) > 2 else None))
-            if x.shape[1] <= 32 and OH >= 4 * x.shape[2] and OW >= 4 * x.shape[3]:
+            if x.shape[1] <= (256 if _losses_module().FUSE_HEAD_WIDE else 32) and OH >= 4 * x.shape[2] and OW >= 4 * x.shape[3]:
                 stats["head_deferred"] += 1
                 return DeferredUpsample(x, (OH, OW))
         return func(*args, **kwargs)

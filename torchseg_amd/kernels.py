@@ -557,6 +557,10 @@ class HipKernels:
     def ohem_up_supported(self, z, OH, OW, thresh):
         return bool(self.lib.tsg_ohem_up_supported(z.shape[1], z.shape[2], z.shape[3], int(OH), int(OW), float(thresh)))
 
+    def ohem_up_wide_supported(self, z, OH, OW):
+        """33 <= C <= 256 classes: ohem_up_fwd / ohem_up_bwd take z on the class-chunked kernels (losses.FUSE_HEAD_WIDE)"""
+        return bool(self.lib.tsg_ohem_up_wide_supported(z.shape[1], z.shape[2], z.shape[3], int(OH), int(OW)))
+
     def ohem_up_fwd(self, z, labels, OH, OW, ignore_label, thresh, min_kept, weight):
         """z [B,C,IH,IW] contiguous low-res logits, labels [B,OH,OW] -> as ohem_fwd"""
         _require_contiguous(z, labels, weight)

@@ -8,6 +8,7 @@ reference's `if self.min_kept > num_valid` / `elif num_valid > 0` are host
 syncs, loss_opr.py:78-80).
 """
 import logging
+import os
 
 import torch
 import torch.nn as nn
@@ -20,6 +21,19 @@ _CITYSCAPES_WEIGHT = [1.4297, 1.4805, 1.4363, 3.365, 2.6635, 1.4311, 2.1943, 1.4
                       15.2588, 5.6818, 2.2067]  # loss_opr.py:57-61
 
 _log = logging.getLogger(__name__)
+
+# TSG_FUSE_HEAD_WIDE=1|0 (default 0, opt-in): heads of 33..256 classes (PSPNet / PSANet on ADE20K: 150) take the fused
+# upsample + criterion kernels as well (tsg_ohem_up_wide_supported).  Off, they materialise the logits.
+FUSE_HEAD_WIDE = os.environ.get("TSG_FUSE_HEAD_WIDE", "0") == "1"
+
+
+def _fused_head_ok(kp, z, OH, OW, thresh):
+    if kp.ohem_up_supported(z, OH, OW, thresh):
+        return True
+    if not FUSE_HEAD_WIDE:
+        return False
+    wide = getattr(kp, "ohem_up_wide_supported", None)   # a provider without the wide kernels materialises
+    return wide is not None and bool(wide(z, OH, OW))
 
 
 class _OhemCEFn(torch.autograd.Function):
@@ -78,7 +92,7 @@ def ohem_cross_entropy(pred, target, ignore_label=255, thresh=0.7, min_kept=0, w
         OH, OW = pred.out_hw
         z = pred.z
         if (target.dim() == 3 and tuple(target.shape) == (z.shape[0], OH, OW)
-                and K.provider().ohem_up_supported(z, OH, OW, thresh)):
+                and _fused_head_ok(K.provider(), z, OH, OW, thresh)):
             loss, sel = _OhemUpCEFn.apply(z, target, OH, OW, int(ignore_label), float(thresh), int(min_kept), weight)
             return (loss, sel) if return_selection else loss
         pred = pred.materialize()
@@ -100,7 +114,6 @@ def check_labels(sel, what="labels"):
 
 
 def _maybe_check_labels(sel):
-    import os
     if os.environ.get("TSG_CHECK_LABELS", "0") == "1":
         check_labels(sel)
 
