@@ -812,6 +812,25 @@ int tsg_cls_head_wgrad(const void* dz, const void* x, float* dw, float* dbias, i
                        void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * The wide classifier convolutions (csrc/clswide.hip) — the same replacement for the heads the group above does not
+ * reach: `nn.Conv2d(512, 150, 1)` / `nn.Conv2d(1024, 150, 1)` + bias of pspnet / psanet network.py (ADE20K) and
+ * `nn.Conv2d(512, 21, 1)` of fcn network.py.  Layouts, rounding points and the meaning of every argument as above.
+ * 1 <= n_classes <= 256; C_in % 64 == 0, 64 <= C_in <= 1024; HW % 4 == 0 (a 90 x 90 map: planes are only 8-byte
+ * aligned, and a group of pixels may lie in two images); B * HW * C_in within the limit of the group above.  The weight
+ * gradient writes S <= 8 fp32 partials per element (S a function of B * HW only) to `ws` and folds them in fp64 in split
+ * order; dbias likewise over the images (B <= 65535).  No atomics: every result is bit-reproducible.
+ * ws: tsg_cls_head_wide_wgrad_ws_bytes (0 for an unsupported shape). */
+int    tsg_cls_head_wide_supported(int dtype, int Cin, int n_classes, int64_t HW);
+int    tsg_cls_head_wide_fwd(const void* x, const float* w, const float* bias, void* z,
+                             int64_t B, int64_t HW, int Cin, int n_classes, void* stream);
+int    tsg_cls_head_wide_dgrad(const void* dz, const float* w, void* dx,
+                               int64_t B, int64_t HW, int Cin, int n_classes, void* stream);
+size_t tsg_cls_head_wide_wgrad_ws_bytes(int64_t B, int64_t HW, int Cin, int n_classes);
+int    tsg_cls_head_wide_wgrad(const void* dz, const void* x, float* dw, float* dbias,
+                               int64_t B, int64_t HW, int Cin, int n_classes,
+                               void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * 1x1 convolution of a globally pooled map (csrc/vecconv.hip) — replaces the cuDNN calls behind the bias-free
  * `ConvBnRelu(C_in, C_out, 1, 1, 0)` layers that follow `nn.AdaptiveAvgPool2d(1)`: furnace/seg_opr/seg_oprs.py:199-205
  * (AttentionRefinement.channel_attention), :222-231 (FeatureFusion.channel_attention), bisenet network.py:34-39

@@ -68,6 +68,9 @@ upsample overrides.  Controlled by env so train.py needs no edit:
                         64 -> 64 stride-1 layers, default gen)
   TSG_CLS_HEAD=1|0      (default 1 on GPU: the 1x1 classifier convolution of a head (<= 32 classes) on tsg_cls_head_*:
                         planar logits for the criterion kernels, no layout copies, no separate bias passes; clshead.py)
+  TSG_CLS_HEAD_WIDE=0|1 (default 0: with TSG_CLS_HEAD, the biased 1x1 classifier convolutions of up to 256 classes and C_in up to
+                        1024 (PSPNet / PSANet on ADE20K: 512 / 1024 -> 150, FCN: 512 -> 21) on tsg_cls_head_wide_*: planar
+                        logits, reproducible weight / bias gradient; read when install_kernels runs; clshead.py)
   TSG_CONV_S2_DGRAD=1|0 (default 1 on GPU: data gradient of the stride-2 3x3 layers other than 64 -> 64 on tsg_conv3x3_s2_dgrad, the
                         shortcut branch's gradient as its epilogue addend; convwrw.py)
   TSG_CAT=1|0           (default 1 on GPU: FeatureFusion's torch.cat([x1, x2], 1) on tsg_cat2_rows; pool.py)
