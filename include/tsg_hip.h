@@ -694,10 +694,13 @@ int tsg_multi_copy_f32(const uint64_t* src, const uint64_t* dst, const int64_t* 
 
 /* bf16 shadows of the fp32 master filters, all refreshed by ONE launch (after the optimizer step) instead of one cast
  * (+ one rotate/transpose) launch per convolution and step.  table_dev: device array of
- *   struct { const float* w; uint16_t* wb; uint16_t* wrt; int32_t n, O, I, pad; }   (tsg_weight_shadow_entry_bytes())
- * wb[i] = bf16(w[i]); for channels_last 3x3 filters (memory [O][kh][kw][I]) and wrt != NULL also
- * wrt[ci][2-kh][2-kw][o] = bf16(w[o][kh][kw][ci]) — what tsg_conv3x3_weight_rot180_t writes.  blockmap_dev / nblocks:
- * tsg_sgd_multi_blockmap over the entries' n. */
+ *   struct { const float* w; uint16_t* wb; uint16_t* wrt; uint16_t* wf0; uint16_t* wf1; int32_t n, O, I, bn0, bn1, pad; }
+ * (64 bytes: tsg_weight_shadow_entry_bytes()).  wb[i] = bf16(w[i]); for channels_last 3x3 filters (memory
+ * [O][kh][kw][I]) and wrt != NULL also wrt[ci][2-kh][2-kw][o] = bf16(w[o][kh][kw][ci]) — what
+ * tsg_conv3x3_weight_rot180_t writes; wf0 / wf1 != NULL: the filter in the fragment order
+ * tsg_conv3x3_gen_prep_filter writes for mode 0 / mode 1 at tile width bn0 / bn1.  blockmap_dev / nblocks: the pairs
+ * {entry, chunk} of tsg_sgd_multi_blockmap over the entries' n; bits 28.. of the chunk word select a block that walks
+ * 4096 destination elements of wf1 (1, with pad bit 0 set) or wf0 (2, with pad bit 1 set) instead of the source. */
 size_t tsg_weight_shadow_entry_bytes(void);
 int tsg_weight_shadow_refresh(const void* table_dev, const int* blockmap_dev, int64_t nblocks, void* stream);
 

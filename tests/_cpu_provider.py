@@ -139,7 +139,8 @@ class OracleProvider:
         w = weight.double()[t] * valid if weight is not None else valid.double()
         denom = w.sum()
         loss = ((w * nll).sum() / denom).float().reshape(1)
-        sel = torch.zeros(8, dtype=torch.int32)
+        sel = torch.zeros(8, dtype=torch.int32)          # {thr, n_kept, num_valid, branch, denominator, n_bad, 0, 0}
+        sel[0:1].view(torch.float32)[0] = float("inf")     # branch 2: no threshold, every valid pixel is kept
         sel[1] = sel[2] = int(valid.sum())
         sel[3] = 2
         sel[4:5].view(torch.float32)[0] = float(denom)

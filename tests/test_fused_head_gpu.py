@@ -200,7 +200,7 @@ def test_benched_head_bf16_uint8_labels_vs_oracle(cuda, IH, regime):
     za = zd.clone().requires_grad_(True)
     loss, sel2 = ohem_cross_entropy(DeferredUpsample(za, (S, S)), t8, 255, 0.7, k, None, return_selection=True)
     loss.backward()
-    assert torch.equal(sel2.cpu()[:4], sel[:4]) and loss.item() == loss_k.item()
+    assert torch.equal(sel2.cpu(), sel) and loss.item() == loss_k.item()
     gref = zr.grad
     err = (za.grad.float().cpu() - gref).abs()
     scale = gref.abs().max().item()

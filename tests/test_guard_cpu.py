@@ -183,7 +183,21 @@ chanscale_fwd chanscale_bwd chanscale_bwd_ds chanscale_bwd_dx cat_channels
 upsample_fwd:float32 upsample_fwd:bfloat16 upsample_fwd+add upsample_fwd_nhwc upsample_presum_fwd:float32
 upsample_presum_fwd:bfloat16 upsample_bwd upsample_bwd_nhwc resize_bilinear_hp:float32 resize_bilinear_hp:bfloat16
 upsample_nearest conv2d_f32_exact_fwd conv2d_f32_exact_dgrad conv2d_f32_exact_wgrad
+ohem_fwd:float32 ohem_fwd:bfloat16 ohem_fwd+weight ohem_fwd+labels_u8
+ohem_bwd:float32 ohem_bwd:bfloat16 ohem_bwd+weight ohem_bwd+labels_u8
+ohem_up_fwd ohem_up_bwd ohem_target_prob kth_value
+focal_fwd:float32 focal_fwd:bfloat16 focal_fwd+labels_u8 focal_bwd:float32 focal_bwd:bfloat16 focal_bwd+labels_u8
+psa_fwd:float32 psa_fwd:bfloat16 psa_bwd:float32 psa_bwd:bfloat16
+confusion_map confusion_map+out confusion_map+labels_u8 confusion_map+out+labels_u8
+confusion_logits:float32 confusion_logits:bfloat16 confusion_logits+out confusion_logits+labels_u8 confusion_logits+out+labels_u8
+seg_tail_logprob:float32 seg_tail_logprob:bfloat16 seg_tail_accum:float32 seg_tail_accum:bfloat16
+seg_tail_accum seg_tail_accum+zflip seg_tail_accum+accumulate seg_tail_accum+zflip+accumulate
+sgd_step sgd_step_dev
+augment_crop augment_crop+gts augment_crop+gts+labels_u8 augment_crop+pad_pixel edge_labels edge_labels+labels_u8
 """.split()
+
+# launches that take raw addresses in tables: a hand-built guarded test each (test_guarded_gpu.HAND_BUILT)
+REQUIRED_BY_HAND = ("sgd_multi_step_dev", "multi_copy", "tsg_weight_shadow_refresh")
 
 
 def test_every_required_entry_point_and_switch_has_a_guarded_case():
@@ -210,7 +224,44 @@ def test_every_required_entry_point_and_switch_has_a_guarded_case():
             assert want <= forms, (v2, bn, sorted(want - forms))
     ids = [c["id"] for c in T.CASES]
     assert len(set(ids)) == len(ids)
+    for name in REQUIRED_BY_HAND:
+        fn = getattr(T, T.HAND_BUILT[name], None)
+        assert callable(fn) and any(m.name == "gpu" for m in getattr(fn, "pytestmark", [])), name
+    # the shapes the criteria, attention, metric, tail and optimizer kernels must keep running at
+    by_family = {}
+    for c in T.CASES:
+        if c["family"] in ("ohem", "ohemup", "focal", "psa", "metric", "segtail", "sgd"):
+            by_family.setdefault(c["family"], set()).add(c["arg"])
+    assert {(2, 19, 33, 47, "confident", 1 / 3, 0.7), (3, 7, 31, 5, "random", 1 / 2, 0.05), (1, 150, 9, 11, "confident", 1 / 4, 0.6),
+            (2, 2, 16, 16, "confident", 1.0, 0.999), (1, 1), (5, 3), (1000, 1000), (65539, 4096)} <= by_family["ohem"]
+    assert len(by_family["ohemup"]) >= 3 and all(a[1] <= 32 for a in by_family["ohemup"])
+    assert {(1, 24, 8, 8), (2, 64, 72, 72), (1, 40, 136, 200), "all_large", "all_very_negative"} <= by_family["psa"]
+    assert {(3, 5, 1, 7), (1, 150, 17, 13), (1, 1, 4, 4)} <= by_family["metric"] and any(a[1] == 192 for a in by_family["metric"])
+    assert (1, 19, 5, 7, 20, 28) in by_family["segtail"]
+    assert {a[1] for a in by_family["segtail"] if len(a) == 6} >= {1, 256}
+    import test_segtail_gpu
+    assert {(n, d) for n in test_segtail_gpu.GEOMS for d in (torch.float32, torch.bfloat16)} <= by_family["segtail"]
+    assert {1, 3, 4095, 4096, 4097, 12289} <= by_family["sgd"] and set(T.MULTI_SIZES) == {1, 3, 4095, 4096, 4097, 12289, 9 * 64 * 64}
+    focal = {a for a in by_family["focal"]}
+    assert {(P, d, l, False) for P in (1, 255, 257, 4099) for d in (torch.float32, torch.bfloat16)
+            for l in (torch.int64, torch.uint8)} <= focal and any(a[3] for a in focal)
     # the issue's shapes of the general and the stride-2 data-gradient kernels are all there
     args = {c["arg"] for c in T.CASES if c["family"] == "conv3g" and isinstance(c["arg"], tuple)}
     assert {(1, 16, 64, 5, 37), (2, 64, 128, 19, 70), (1, 32, 192, 1, 1), (2, 96, 64, 33, 31), (3, 256, 64, 9, 33),
             (1, 32, 32, 7, 9), (1, 64, 96, 33, 31), (3, 32, 64, 1, 1), (2, 96, 32, 20, 130)} <= args
+
+
+def test_the_cpu_stand_in_returns_the_documented_selection_words():
+    """sel[8] = {thr, n_kept, num_valid, branch, denominator, n_bad, 0, 0} (include/tsg_hip.h): the stand-in provider of the
+    host-logic tests hands out the same eight words as the kernels, the two spare ones zero"""
+    from _cpu_provider import OracleProvider
+    g = torch.Generator().manual_seed(0)
+    z = torch.randn(2, 5, 3, 4, generator=g)
+    t = torch.randint(0, 5, (2, 3, 4), generator=g)
+    t[0, 0] = 255
+    t[1, 1, 1] = 7                                                   # neither a class nor the ignore value: n_bad
+    loss, nll, lse, sel = OracleProvider().ohem_fwd(z, t, 255, 1.0, 0, None)
+    valid = int(((t != 255) & (t < 5)).sum())
+    assert sel.dtype == torch.int32 and tuple(sel.shape) == (8,)
+    assert sel[1:4].tolist() == [valid, valid, 2] and int(sel[5]) == 1 and sel[6:].tolist() == [0, 0]
+    assert sel[4:5].view(torch.float32).item() == float(valid) and sel[0:1].view(torch.float32).item() == float("inf")

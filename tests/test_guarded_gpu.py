@@ -9,11 +9,17 @@ callers are the families' own test functions and `_check` helpers, imported from
 shapes: their oracle assertions, with the project's bounds, therefore judge the guarded 0xFF result.  No tolerance is
 stated in this file; every comparison it adds itself is exact.
 
+In-place launches: a call with out= (or dst, the accumulator of seg_tail_accum) hands the caller their own tensor back,
+bit-identical to the guarded results; sgd_step / sgd_step_dev return nothing, and the comparison of the operands
+afterwards is their check.  Launches that take raw addresses in tables (HAND_BUILT) cannot be interposed: each has a
+hand-built test at the end of this file.
+
 CASES is the driver table: (family, case id, callable, argument, switches, the launch forms the case must reach under
 guard).  tests/test_guard_cpu.py diffs it against the list of entry points and switches that must stay covered."""
 import inspect
 import os
 
+import numpy as np
 import pytest
 import torch
 
@@ -35,22 +41,44 @@ maxpool_fwd maxpool_bwd gap_fwd gap_bwd adaptive_avgpool_fwd adaptive_avgpool_bw
 chanscale_fwd chanscale_bwd chanscale_bwd_ds chanscale_bwd_dx cat_channels
 upsample_fwd upsample_fwd_nhwc upsample_presum_fwd upsample_bwd upsample_bwd_nhwc resize_bilinear_hp upsample_nearest
 conv2d_f32_exact_fwd conv2d_f32_exact_dgrad conv2d_f32_exact_wgrad
+ohem_fwd ohem_bwd ohem_up_fwd ohem_up_bwd ohem_target_prob kth_value focal_fwd focal_bwd
+psa_fwd psa_bwd confusion_map confusion_logits seg_tail_logprob seg_tail_accum
+sgd_step sgd_step_dev augment_crop edge_labels
 """.split()
+
+# launches that take raw addresses in host or device tables: the interposer cannot wrap their operands, so each has a
+# hand-built test below that places every segment in an arena of its own (tests/test_guard_cpu.py checks the names)
+HAND_BUILT = {"sgd_multi_step_dev": "test_sgd_multi_step_under_guard", "multi_copy": "test_multi_copy_under_guard",
+              "tsg_weight_shadow_refresh": "test_weight_shadow_refresh_under_guard"}
 
 # -> (partial [S_max, 2, C], S): the launch decides how many partial rows it needs and returns that count; the rows
 # behind it are not part of the result (every consumer folds partial[:S]), so the comparison stops at S
 _ROWS_RETURNED = ("bn_stats", "bn_bwd_reduce", "bn_bwd_reduce_bits", "bn_bwd_reduce_mixed")
 
 # arguments that make a launch form of their own: "+name" joins the method's name when the argument is given / true
-_FORM_ARGS = ("with_stats", "in_ab", "addend", "addend_sub", "bsum", "out", "xc", "residual", "add", "accumulate")
+_FORM_ARGS = ("with_stats", "in_ab", "addend", "addend_sub", "bsum", "zflip", "out", "xc", "residual", "add", "accumulate")
+# an argument named `out` that is an operand, not a destination
+_OUT_IS_AN_OPERAND = ("psa_bwd",)
+# the argument a launch updates in place and hands back (out=; dst of seg_tail_accum): the caller gets their own tensor
+_IN_PLACE = ("out", "dst")
 
 
 def _form(name, args):
     f = name
+    if name.startswith("ohem_") and args.get("weight") is not None:    # the optional class-weight table of the criteria
+        f += "+weight"
     for k in _FORM_ARGS:
         v = args.get(k)
-        if v is not None and v is not False:
+        if v is not None and v is not False and not (k == "out" and name in _OUT_IS_AN_OPERAND):
             f += "+" + k
+    if name == "augment_crop":
+        if args.get("gts") is not None:
+            f += "+gts"
+        if args["pad_pixel"] >= 0:
+            f += "+pad_pixel"
+    labels = [args.get(k) for k in ("labels", "target", "gt")]
+    if any(isinstance(v, torch.Tensor) and v.dtype == torch.uint8 for v in labels) or args.get("label_dtype") is torch.uint8:
+        f += "+labels_u8"
     if args.get("stride") == 2:
         f += "+stride2"
     if name == "conv3x3_wrw" and args.get("variant"):
@@ -65,6 +93,15 @@ def _wrap(o, fill):
         return _guard.guarded(o.detach(), fill)
     if isinstance(o, (tuple, list)):
         return type(o)(_wrap(v, fill) for v in o)
+    return o
+
+
+def _comparable(o):
+    """host arrays among the operands (geometry tables, mean / std) as tensors, for assert_bit_identical"""
+    if isinstance(o, np.ndarray):
+        return torch.from_numpy(np.ascontiguousarray(o))
+    if isinstance(o, (tuple, list)):
+        return type(o)(_comparable(v) for v in o)
     return o
 
 
@@ -125,12 +162,12 @@ class UnderGuard:
             # the operands afterwards: nothing but a documented in-place result (out=, running statistics) may have
             # changed, and that equally in the three calls
             keys = sorted(args)
-            _guard.assert_bit_identical([tuple(x[k] for k in keys) for x in after], names)
+            _guard.assert_bit_identical([tuple(_comparable(x[k]) for k in keys) for x in after], names)
             ctx.hits.add(form)
             ctx.hits.add(name)
             if dt is not None:
                 ctx.hits.add("%s:%s" % (name, str(dt).replace("torch.", "")))
-            if args.get("out") is not None:
+            if name not in _OUT_IS_AN_OPERAND and any(args.get(k) is not None for k in _IN_PLACE):
                 return results[2]                         # the caller's own tensor, bit-identical to the guarded results
             return _detached(results[0])
 
@@ -143,6 +180,7 @@ def _mods():
     import test_bn_gpu, test_bnconv_gpu, test_clshead_gpu, test_conv3g_gpu, test_conv64_gpu, test_convwrw_gpu
     import test_deepstem_gpu, test_dilconv_gpu, test_dwconv_gpu, test_exactconv_gpu, test_pool_gpu, test_stemconv_gpu
     import test_stemfuse_gpu, test_stempool_gpu, test_upsample_gpu, test_vecconv_gpu
+    import test_augment_gpu, test_focal_gpu, test_fused_head_gpu, test_metric_gpu, test_ohem_gpu, test_psa_gpu, test_segtail_gpu
     return locals()
 
 
@@ -516,6 +554,252 @@ _add("upsample", resize_hp, [(2, 3, 7, 5, 13, 9), (1, 19, 9, 11, 5, 31)],
 _add("convf32", exactconv, EXACT_CASES, ["conv2d_f32_exact_fwd", "conv2d_f32_exact_dgrad", "conv2d_f32_exact_wgrad"])
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# criteria, attention, metric, evaluation tail, optimizer, pre-processing
+def _same_run(a, b):
+    """two results of test_ohem_gpu._run -> equal bit for bit (loss, gradient, selection)"""
+    assert a[0] == b[0] or (a[0] != a[0] and b[0] != b[0]), (a[0], b[0])
+    _guard.assert_bit_identical([a[1], b[1]], ["int64 labels", "uint8 labels"])
+    assert a[2] == b[2], (a[2], b[2])
+
+
+def ohem(cuda, case, mp):
+    """fp32 and bf16 logits against the oracle; uint8 labels give what int64 labels give, bit for bit"""
+    m = _mods()["test_ohem_gpu"]
+    B, C, H, W, regime, frac, thresh = case
+    m.test_ohem_vs_oracle_fp32(cuda, case)
+    m.test_ohem_bf16(cuda, case)
+    pred, t = m._make(B, C, H, W, regime, seed=B * 1000 + H)
+    k = int(B * H * W * frac)
+    for dtype in (torch.float32, torch.bfloat16):
+        _same_run(m._run(cuda, pred, t, thresh, k, dtype=dtype), m._run(cuda, pred, t, thresh, k, dtype=dtype, ltype=torch.uint8))
+
+
+def ohem_more_than_valid(cuda, case, mp):
+    """min_kept > num_valid: no mining (branch 2), every valid pixel kept"""
+    m = _mods()["test_ohem_gpu"]
+    B, C, H, W, regime, frac, thresh = case
+    _, t = m._make(B, C, H, W, regime, seed=B * 1000 + H)
+    assert int(B * H * W * frac) > int((t != 255).sum()) > 0
+    dev = m._check_vs_oracle(cuda, case)
+    assert dev["branch"] == 2 and dev["n_kept"] == dev["num_valid"] == int((t != 255).sum())
+
+
+def ohem_all_ignored(cuda, shape, mp):
+    """every label ignored: loss NaN (a mean over no pixel), nll == 0 everywhere, n_kept == 0, gradient all zero"""
+    kp = _kp()
+    B, C, H, W = shape
+    g = torch.Generator().manual_seed(sum(shape))
+    pred = torch.randn(B, C, H, W, generator=g)
+    for dtype in (torch.float32, torch.bfloat16):
+        for ltype in (torch.int64, torch.uint8):
+            p = pred.to(dtype).to(cuda)
+            t = torch.full((B, H, W), 255, dtype=ltype, device=cuda)
+            loss, nll, lse, sel = kp.ohem_fwd(p, t, 255, 0.7, B * H * W // 4, None)
+            s = sel.cpu()
+            assert bool(torch.isnan(loss).all()) and not bool(nll.any())
+            assert int(s[1]) == 0 and int(s[2]) == 0 and int(s[3]) == 2 and int(s[5]) == 0 and int(s[6]) == 0 and int(s[7]) == 0
+            d = kp.ohem_bwd(p, t, 255, None, nll, lse, sel, torch.ones(1, device=cuda))
+            assert d.dtype == dtype and d.shape == p.shape and not bool(d.float().any()), "gradient of an all-ignored batch"
+
+
+def ohem_weights(cuda, arg, mp):
+    _mods()["test_ohem_gpu"].test_ohem_class_weights_vs_oracle_fp32(cuda, *arg)
+
+
+def ohem_target_prob(cuda, shape, mp):
+    _mods()["test_ohem_gpu"].test_ohem_selection_bit_exact_given_device_probs(cuda, shapes=(shape,))
+
+
+def kth(cuda, nk, mp):
+    _mods()["test_ohem_gpu"].test_kth_value_bit_exact(cuda, *nk)
+
+
+def ohem_up(cuda, case, mp):
+    kp = _kp()
+    B, C, IH, IW, OH, OW, regime, frac, thresh = case
+    assert kp.ohem_up_supported(torch.empty(B, C, IH, IW, device="meta"), OH, OW, thresh), "the narrow fused head must take this shape"
+    _mods()["test_fused_head_gpu"].test_fused_head_vs_oracle_fp32(cuda, case)
+
+
+def focal(cuda, case, mp):
+    _mods()["test_focal_gpu"].test_focal_vs_oracle(cuda, *case)
+
+
+def psa(cuda, shape, mp):
+    m = _mods()["test_psa_gpu"]
+    m.test_psa_fp32(cuda, shape)
+    m.test_psa_bf16(cuda, shape)
+
+
+def psa_outside_range(cuda, regime, mp):
+    """the flag and the three-launch redo of the bf16 forward over a poisoned workspace"""
+    _mods()["test_psa_gpu"].test_psa_bf16_logits_outside_the_optimistic_range_take_the_guarded_path(
+        cuda, regime, shape=(1, 64, 264, 200))
+
+
+def confusion(cuda, shape, mp):
+    m = _mods()["test_metric_gpu"]
+    for dtype in (torch.float32, torch.bfloat16):
+        m.test_hist_info_from_logits_vs_oracle(cuda, dtype, shape)
+
+
+def confusion_out_twice(cuda, shape, mp):
+    """out= accumulates: a second call into the same tensor adds the same counts"""
+    kp = _kp()
+    B, C, H, W = shape
+    g = torch.Generator().manual_seed(sum(shape))
+    z = torch.randn(B, C, H, W, generator=g).to(cuda)
+    gt = torch.randint(0, C, (B, H, W), generator=g)
+    gt[torch.rand(B, H, W, generator=g) < 0.2] = 255
+    pred = z.argmax(1)
+    for labels in (gt.to(cuda), gt.to(torch.uint8).to(cuda)):
+        for first, call in ((kp.confusion_map(pred, labels, C), lambda o: kp.confusion_map(pred, labels, C, out=o)),
+                            (kp.confusion_logits(z, labels, C), lambda o: kp.confusion_logits(z, labels, C, out=o))):
+            once = first.clone()
+            assert int(once[:C * C].sum()) == int((gt != 255).sum()) > 0
+            assert call(first) is first and torch.equal(first, 2 * once)
+            assert call(first) is first and torch.equal(first, 3 * once)
+
+
+def segtail_logprob(cuda, case, mp):
+    m = _mods()["test_segtail_gpu"]
+    for dtype in (torch.float32, torch.bfloat16):
+        m.test_logprob_matches_float64(cuda, *case, dtype)
+
+
+def segtail_accum(cuda, arg, mp):
+    m = _mods()["test_segtail_gpu"]
+    name, dtype = arg
+    for flip in (False, True):
+        for accumulate in (False, True):
+            m.test_accum_matches_reference_loop(cuda, name, flip, accumulate, dtype)
+
+
+def _sgd_ref(p, g, b, lr, mom, wd, gs, first=False):
+    """float64: d = g * gs + wd * p; b = d (first step) or mom * b + d; p -= lr * b (torch.optim.SGD, dampening 0)"""
+    d = g * gs + wd * p
+    b = d if first else mom * b + d
+    return p - lr * b, b
+
+
+def _close(got, want):
+    torch.testing.assert_close(got.double().cpu(), want, rtol=1e-5, atol=1e-6)     # the bound of tests/test_optim_gpu.py
+
+
+def sgd_single(cuda, n, mp):
+    """tsg_sgd_step (host lr, `first` ignores the buffer's content) and tsg_sgd_step_dev (device lr, zeroed buffer), two
+    steps each, against the float64 update; both return nothing and update their operands"""
+    kp = _kp()
+    gen = torch.Generator().manual_seed(n)
+    p0, g1, g2 = (torch.randn(n, generator=gen) for _ in range(3))
+    lr, mom, wd, gs = 0.05, 0.9, 5e-4, 0.5
+    rp, rb = _sgd_ref(p0.double(), g1.double(), None, lr, mom, wd, gs, first=True)
+    rp2, rb2 = _sgd_ref(rp, g2.double(), rb, lr, mom, wd, gs)
+    p, b = p0.to(cuda), torch.full((n,), float("nan"), device=cuda)
+    assert kp.sgd_step(p, g1.to(cuda), b, lr, mom, wd, gs, 1) is None
+    _close(p, rp), _close(b, rb)
+    kp.sgd_step(p, g2.to(cuda), b, lr, mom, wd, gs, 0)
+    _close(p, rp2), _close(b, rb2)
+    lr_dev = torch.tensor([0.1], device=cuda)                       # lr = lr_dev[0] * lr_mult
+    rp, rb = _sgd_ref(p0.double(), g1.double(), torch.zeros(n, dtype=torch.float64), lr, mom, wd, gs)
+    rp2, rb2 = _sgd_ref(rp, g2.double(), rb, lr, mom, wd, gs)
+    p, b = p0.to(cuda), torch.zeros(n, device=cuda)
+    assert kp.sgd_step_dev(p, g1.to(cuda), b, lr_dev, 0.5, mom, wd, gs) is None
+    _close(p, rp), _close(b, rb)
+    kp.sgd_step_dev(p, g2.to(cuda), b, lr_dev, 0.5, mom, wd, gs)
+    _close(p, rp2), _close(b, rb2)
+    assert bool(torch.equal(lr_dev.cpu(), torch.tensor([0.1])))
+
+
+def augment(cuda, case, mp):
+    m = _mods()["test_augment_gpu"]
+    for label_dtype in (torch.int64, torch.uint8):
+        m.test_augment_matches_oracle(cuda, case, label_dtype)
+
+
+def augment_image_only(cuda, case, mp):
+    """gts=None gives the image of the call with labels, bit for bit; pad_pixel >= 0 changes the padded pixels alone, to
+    (pad_pixel / 255 - mean) / std formed in fp32 as the library's host code forms it"""
+    m = _mods()["test_augment_gpu"]
+    kp = _kp()
+    (H, W), crop, p = case
+    img, gt = m._sample(H, W, H + W)
+    gt[gt == 255] = 0                                              # 255 in the label output then marks the padding alone
+    imgs, gts = [torch.from_numpy(img).to(cuda)], [torch.from_numpy(gt).to(cuda)]
+    geom = np.array([[H, W, int(H * p["scale"]), int(W * p["scale"]), int(p["flip"]), p["crop_y"], p["crop_x"]]], dtype=np.int32)
+    mean, std = m.MEAN.astype(np.float32), m.STD.astype(np.float32)
+    with_gt, lab = kp.augment_crop(imgs, gts, geom, crop, mean, std)
+    alone, none = kp.augment_crop(imgs, None, geom, crop, mean, std)
+    assert none is None and torch.equal(alone, with_gt)
+    raw, _ = kp.augment_crop(imgs, None, geom, crop, mean, std, pad_pixel=7.0)
+    pad = (lab == 255)[:, None].expand_as(raw)
+    assert torch.equal(raw[~pad], with_gt[~pad])
+    if bool(pad.any()):
+        assert not bool(with_gt[pad].any())                        # pad_pixel < 0: the normalised image is padded with 0
+        for c in range(3):
+            want = (np.float32(7.0) / np.float32(255.0) - mean[c]) * (np.float32(1.0) / std[c])
+            got = raw[:, c][lab == 255]
+            assert bool((got == float(want)).all()), (c, float(want), got.unique().tolist())
+
+
+def edge(cuda, case, mp):
+    m = _mods()["test_augment_gpu"]
+    for label_dtype in (torch.int64, torch.uint8):
+        m.test_dfn_edge_labels_match_oracle(cuda, case, label_dtype)
+
+
+from test_augment_gpu import CASES as AUG_CASES                                       # module level: the tables below
+from test_focal_gpu import FOCAL_CASES
+from test_fused_head_gpu import CASES as HEAD_CASES
+from test_ohem_gpu import WEIGHTED as OHEM_WEIGHTED
+from test_segtail_gpu import GEOMS as SEGTAIL_GEOMS
+
+OHEM_CASES = [(2, 19, 33, 47, "confident", 1 / 3, 0.7), (3, 7, 31, 5, "random", 1 / 2, 0.05), (1, 150, 9, 11, "confident", 1 / 4, 0.6),
+              (2, 2, 16, 16, "confident", 1.0, 0.999)]
+_OHEM_FORMS = ["ohem_fwd:float32", "ohem_fwd:bfloat16", "ohem_fwd+labels_u8", "ohem_bwd:float32", "ohem_bwd:bfloat16",
+               "ohem_bwd+labels_u8"]
+# the two smallest narrow (C <= 32) entries of test_fused_head_gpu.CASES, and a ragged one: IH, IW odd, OH no multiple of
+# the 32-row band, OW = 301 one full 256-column tile and a partial one
+OHEM_UP_CASES = sorted((c for c in HEAD_CASES if c[1] <= 32), key=lambda c: c[0] * c[1] * c[4] * c[5])[:2] + \
+    [(1, 7, 5, 37, 21, 301, "confident", 1 / 3, 0.7)]
+PSA_SHAPES = [(1, 24, 8, 8), (2, 64, 72, 72), (1, 40, 136, 200)]
+CONFUSION_SHAPES = [(3, 5, 1, 7), (1, 150, 17, 13), (1, 1, 4, 4), (1, 192, 3, 5)]      # the last: n_cl = 192, the kernels' limit
+SEGTAIL_CASES = [(1, 19, 5, 7, 20, 28), (2, 1, 3, 5, 9, 13), (1, 256, 4, 4, 13, 10)]   # C = 1; C = 256 on a 4x4 map
+SGD_SIZES = [1, 3, 4095, 4096, 4097, 12289]                                             # the chunk is 4096 elements
+EDGE_CASES = AUG_CASES[:7] + [((256, 512), (192, 192), dict(flip=True, scale=1.75, crop_y=100, crop_x=300))]
+
+_add("ohem", ohem, OHEM_CASES, _OHEM_FORMS)
+_add("ohem", ohem_more_than_valid, [(1, 5, 16, 16, "random", 0.97, 0.5)], ["ohem_fwd", "ohem_bwd"])
+_add("ohem", ohem_all_ignored, [(2, 5, 7, 9)], _OHEM_FORMS)
+_add("ohem", ohem_weights, OHEM_WEIGHTED, ["ohem_fwd+weight", "ohem_bwd+weight"])
+_add("ohem", ohem_target_prob, [(3, 7, 31, 5, "random", 0.9)], ["ohem_target_prob", "ohem_fwd", "ohem_bwd"])
+_add("ohem", kth, [(1, 1), (5, 3), (1000, 1000), (65539, 4096)], ["kth_value"])
+_add("ohemup", ohem_up, OHEM_UP_CASES, ["ohem_up_fwd", "ohem_up_bwd"])
+for _c in FOCAL_CASES:
+    _dt = str(_c[1]).replace("torch.", "")
+    _add("focal", focal, [_c], ["focal_fwd:" + _dt, "focal_bwd:" + _dt] +
+         (["focal_fwd+labels_u8", "focal_bwd+labels_u8"] if _c[2] is torch.uint8 else ["focal_fwd", "focal_bwd"]))
+_add("psa", psa, PSA_SHAPES, ["psa_fwd:float32", "psa_fwd:bfloat16", "psa_bwd:float32", "psa_bwd:bfloat16"])
+_add("psa", psa_outside_range, ["all_large", "all_very_negative"], ["psa_fwd:bfloat16", "psa_bwd:bfloat16"])
+_add("metric", confusion, [s for s in CONFUSION_SHAPES if s[1] > 2],
+     ["confusion_logits:float32", "confusion_logits:bfloat16", "confusion_logits+out", "confusion_map", "confusion_map+out+labels_u8"])
+_add("metric", confusion, [s for s in CONFUSION_SHAPES if s[1] <= 2],
+     ["confusion_logits:float32", "confusion_logits:bfloat16", "confusion_logits+out", "confusion_map+out+labels_u8"])
+_add("metric", confusion_out_twice, [(3, 5, 1, 7), (1, 150, 17, 13)],
+     ["confusion_map", "confusion_map+out", "confusion_map+labels_u8", "confusion_map+out+labels_u8", "confusion_logits",
+      "confusion_logits+out", "confusion_logits+labels_u8", "confusion_logits+out+labels_u8"])
+_add("segtail", segtail_logprob, SEGTAIL_CASES, ["seg_tail_logprob:float32", "seg_tail_logprob:bfloat16"])
+for _dt in (torch.float32, torch.bfloat16):
+    _add("segtail", segtail_accum, [(n, _dt) for n in sorted(SEGTAIL_GEOMS)],
+         ["seg_tail_accum", "seg_tail_accum+zflip", "seg_tail_accum+accumulate", "seg_tail_accum+zflip+accumulate",
+          "seg_tail_accum:" + str(_dt).replace("torch.", "")])
+_add("sgd", sgd_single, SGD_SIZES, ["sgd_step", "sgd_step_dev"])
+_add("augment", augment, AUG_CASES, ["augment_crop+gts", "augment_crop+gts+labels_u8"])
+_add("augment", augment_image_only, AUG_CASES[:7], ["augment_crop", "augment_crop+pad_pixel", "augment_crop+gts"])
+_add("augment", edge, EDGE_CASES, ["edge_labels", "edge_labels+labels_u8", "augment_crop+gts", "augment_crop+gts+labels_u8"])
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", CASES, ids=[c["id"] for c in CASES])
 def test_under_guard(cuda, case, monkeypatch):
@@ -530,3 +814,147 @@ def test_under_guard(cuda, case, monkeypatch):
         kp._npart.clear()
     missing = [f for f in case["forms"] if f not in ug.hits]
     assert not missing, ("launch forms this case must reach under guard but did not", missing, sorted(ug.hits))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the launches that take addresses (HAND_BUILT): every segment in an arena of its own, the tables built from those
+# data_ptr()s, under both fills and plain; the guards, bit-identity of every segment, and the plain reference of the operation
+MULTI_SIZES = SGD_SIZES + [9 * 64 * 64]
+_UNALIGNED = 2                  # this segment's gradient / source starts 4 bytes off a 16-byte boundary: the scalar path
+
+
+def _three_ways(run):
+    """run(place, empty) under both fills and plain -> the three results, guards checked, bit-identical"""
+    results, names = [], []
+    for fill in _guard.FILLS:
+        with _guard.Guarded(fill) as g:
+            out = run(g.guarded, g.module.__dict__["torch"].empty)
+        g.check()
+        results.append(out)
+        names.append("guarded 0x%02X" % fill)
+    results.append(run(lambda t: t.clone(), torch.empty))
+    names.append("plain")
+    _guard.assert_bit_identical(results, names)
+    return results[0]
+
+
+@pytest.mark.gpu
+def test_sgd_multi_step_under_guard(cuda):
+    """tsg_sgd_multi_step_dev: segments of 1, 3, 4095, 4096, 4097, 12289 and 9*64*64 elements in two parameter groups,
+    two steps from zeroed momentum buffers, against the float64 update at the bound of tests/test_optim_gpu.py"""
+    kp = _kp()
+    gen = torch.Generator().manual_seed(11)
+    p0 = [torch.randn(n, generator=gen) for n in MULTI_SIZES]
+    grads = [[torch.randn(n, generator=gen) for n in MULTI_SIZES] for _ in range(2)]
+    group = np.array([i % 2 for i in range(len(MULTI_SIZES))], dtype=np.int32)
+    numel = np.array(MULTI_SIZES, dtype=np.int64)
+    lr, mom, wd, gs = [0.05, 0.5], np.array([0.9, 0.5], dtype=np.float32), np.array([5e-4, 0.0], dtype=np.float32), 0.25
+
+    def run(place, empty):
+        ps = [place(t.to(cuda)) for t in p0]
+        bs = [place(torch.zeros(n, device=cuda)) for n in MULTI_SIZES]
+        lr_dev = place(torch.tensor(lr, device=cuda))
+        bmap = place(kp.sgd_multi_blockmap(numel, cuda))
+        for step in range(2):
+            gr = []
+            for i, t in enumerate(grads[step]):
+                if i == _UNALIGNED:
+                    gr.append(place(torch.cat([torch.zeros(1), t]).to(cuda))[1:])
+                    assert gr[-1].data_ptr() % 16 == 4
+                else:
+                    gr.append(place(t.to(cuda)))
+            ptrs = np.array([[t.data_ptr() for t in ps], [t.data_ptr() for t in gr], [t.data_ptr() for t in bs]], dtype=np.uint64)
+            kp.sgd_multi_step_dev(ptrs, numel, group, lr_dev, mom, wd, bmap, grad_scale=gs)
+            torch.cuda.synchronize()
+        return tuple(ps) + tuple(bs) + tuple(gr) + (lr_dev, bmap)
+
+    out = _three_ways(run)
+    for i, n in enumerate(MULTI_SIZES):
+        gi = int(group[i])
+        rp, rb = p0[i].double(), torch.zeros(n, dtype=torch.float64)
+        for step in range(2):
+            rp, rb = _sgd_ref(rp, grads[step][i].double(), rb, lr[gi], float(mom[gi]), float(wd[gi]), gs)
+        _close(out[i], rp), _close(out[len(MULTI_SIZES) + i], rb)
+        assert torch.equal(out[2 * len(MULTI_SIZES) + i].cpu(), grads[1][i])           # the gradients are read only
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("with_map", [False, True])
+def test_multi_copy_under_guard(cuda, with_map):
+    """tsg_multi_copy_f32: dst[i] = scale * src[i], exact (one fp32 multiplication per element), into destinations that
+    hold the fill; one source and one destination start off a 16-byte boundary"""
+    kp = _kp()
+    gen = torch.Generator().manual_seed(12)
+    src = [torch.randn(n, generator=gen) for n in MULTI_SIZES]
+    scale = 0.3
+
+    def run(place, empty):
+        ss = [place(torch.cat([torch.zeros(1), t]).to(cuda))[1:] if i == _UNALIGNED else place(t.to(cuda)) for i, t in enumerate(src)]
+        ds = [empty(n + 1, dtype=torch.float32, device=cuda)[1:] if i == _UNALIGNED + 1 else empty(n, dtype=torch.float32, device=cuda)
+              for i, n in enumerate(MULTI_SIZES)]
+        bmap = place(kp.sgd_multi_blockmap(np.array(MULTI_SIZES, dtype=np.int64), cuda)) if with_map else None
+        back = kp.multi_copy(ss, ds, blockmap=bmap, scale=scale)
+        torch.cuda.synchronize()
+        assert bmap is None or back is bmap
+        return tuple(ds) + tuple(ss)
+
+    out = _three_ways(run)
+    for i, t in enumerate(src):
+        assert torch.equal(out[i].cpu(), t * torch.tensor(scale, dtype=torch.float32)), MULTI_SIZES[i]
+        assert torch.equal(out[len(src) + i].cpu(), t)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("own_pass", [True, False])
+def test_weight_shadow_refresh_under_guard(cuda, own_pass, monkeypatch):
+    """tsg_weight_shadow_refresh through torchseg_amd.shadow._Bank: the masters copied into arenas, every shadow (bf16
+    cast, rot180-transpose, both fragment-order images) allocated by the bank inside arenas that hold the fill.  Exact:
+    wb = bf16(w), wrt = the rot180-transpose of tests/test_convwrw_gpu.py, the fragment images what
+    tsg_conv3x3_gen_prep_filter writes.  own_pass False: every image written by the blocks that walk the source."""
+    from torchseg_amd import shadow
+    kp = _kp()
+    monkeypatch.setattr(shadow, "_WF1_PASS", own_pass)
+    gen = torch.Generator().manual_seed(13)
+    filters = [torch.randn(*s, generator=gen).to(cuda).contiguous(memory_format=torch.channels_last)
+               for s in [(64, 32, 3, 3), (32, 64, 3, 3), (96, 32, 3, 3)]]
+    plain = [torch.randn(n, generator=gen).to(cuda) for n in (5, 4097)]          # 1-D parameters: the cast alone
+
+    def run(place):
+        bank = shadow._Bank()
+        ws, vs = [place(w) for w in filters], [place(v) for v in plain]
+        out = []
+        for w in ws:
+            wb, wrt = bank.get(w, want_rot=True)
+            out += [wb, wrt, bank.get_gen(w, 0, 32), bank.get_gen(w, 1, 32)]
+        for v in vs:
+            out.append(bank.get(v)[0])
+        with torch.no_grad():
+            ws[1].mul_(1.5)                              # a change torch sees: one launch rewrites every shadow
+        out.append(bank.get(ws[1], want_rot=True)[0])
+        torch.cuda.synchronize()
+        return tuple(out) + tuple(ws) + tuple(vs)
+
+    results, names = [], []
+    for fill in _guard.FILLS:
+        with _guard.Guarded(fill, prov=None, module=shadow) as g:
+            out = run(g.guarded)
+        g.check()
+        results.append(out)
+        names.append("guarded 0x%02X" % fill)
+    results.append(run(lambda t: t.clone()))
+    names.append("plain")
+    _guard.assert_bit_identical(results, names)
+    out = results[0]
+    for i, w0 in enumerate(filters):
+        w = w0 * 1.5 if i == 1 else w0
+        wb, wrt, wf0, wf1 = out[4 * i:4 * i + 4]
+        assert wb.stride() == w.stride() and torch.equal(wb, w.to(torch.bfloat16))
+        assert wrt.is_contiguous(memory_format=torch.channels_last) and torch.equal(wrt, w.flip(2, 3).transpose(0, 1).to(torch.bfloat16))
+        O, I = w.shape[0], w.shape[1]
+        for mode, got in ((0, wf0), (1, wf1)):
+            like = torch.empty(1, O if mode else I, 8, 8, device=cuda)
+            assert torch.equal(got, kp.conv3x3_gen_prep_filter(w, mode, like, bn=32)[0]), (tuple(w.shape), mode)
+    n = 4 * len(filters)
+    for j, v in enumerate(plain):
+        assert torch.equal(out[n + j], v.to(torch.bfloat16))
+    assert torch.equal(out[n + len(plain)], (filters[1] * 1.5).to(torch.bfloat16))

@@ -97,15 +97,14 @@ def _make(B, C, H, W, regime, seed):
     return pred, t
 
 
-@pytest.mark.parametrize("case", CASES)
-def test_ohem_vs_oracle_fp32(cuda, case):
+def _check_vs_oracle(cuda, case, weight=None):
     B, C, H, W, regime, frac, thresh = case
     pred, t = _make(B, C, H, W, regime, seed=B * 1000 + H)
     min_kept = int(B * H * W * frac)
     p = pred.clone().requires_grad_(True)
-    ref_loss, info = ohem_ref.ohem_cross_entropy(p, t, 255, thresh, min_kept, None, return_info=True)
+    ref_loss, info = ohem_ref.ohem_cross_entropy(p, t, 255, thresh, min_kept, weight, return_info=True)
     ref_loss.backward()
-    loss, grad, dev = _run(cuda, pred, t, thresh, min_kept)
+    loss, grad, dev = _run(cuda, pred, t, thresh, min_kept, weight)
     assert dev["num_valid"] == info["num_valid"]
     assert dev["branch"] == info["branch"], (dev, info["branch"])
     assert abs(loss - ref_loss.item()) <= 1e-4 * max(1.0, abs(ref_loss.item()))
@@ -121,9 +120,32 @@ def test_ohem_vs_oracle_fp32(cuda, case):
         assert abs(dev["thr"] - info["threshold"]) <= 4e-7 * info["threshold"]
     ok = ~near[:, None].repeat(C, 1)
     np.testing.assert_allclose(grad.numpy()[ok], p.grad.numpy()[ok], rtol=2e-4, atol=1e-7)
+    return dev
 
 
-def test_ohem_selection_bit_exact_given_device_probs(cuda):
+@pytest.mark.parametrize("case", CASES)
+def test_ohem_vs_oracle_fp32(cuda, case):
+    _check_vs_oracle(cuda, case)
+
+
+# class weights (loss_opr.py:57-63): nn.CrossEntropyLoss(weight=...) over the kept pixels = sum(w_t nll) / sum(w_t), at
+# the bounds of the unweighted test; one case per threshold branch (0: thr == thresh, 1: the k-th value)
+WEIGHTED = [((2, 19, 33, 47, "confident", 1 / 16, 0.7), 0), ((3, 7, 31, 5, "random", 1 / 2, 0.05), 1)]
+
+
+@pytest.mark.parametrize("case,branch", WEIGHTED)
+def test_ohem_class_weights_vs_oracle_fp32(cuda, case, branch):
+    C = case[1]
+    w = torch.tensor(ohem_ref.CITYSCAPES_WEIGHT) if C == 19 else \
+        torch.rand(C, generator=torch.Generator().manual_seed(C)) * 3.0 + 0.25
+    dev = _check_vs_oracle(cuda, case, w)
+    assert dev["branch"] == branch
+
+
+_SELECTION_SHAPES = ((2, 19, 128, 128, "confident", 0.5), (1, 19, 512, 512, "confident", 1 / 4), (3, 7, 31, 5, "random", 0.9))
+
+
+def test_ohem_selection_bit_exact_given_device_probs(cuda, shapes=_SELECTION_SHAPES):
     """The selection contract, bit for bit (north_star: "bit-exact for OHEM top-k indices"): with p_t as the device
     computes it (tsg_ohem_target_prob: the kernels' own exp(-nll)), the threshold equals torch.sort(p_t)[k-1]
     (loss_opr.py:86-89) exactly and the kept set is exactly {valid & p_t <= thr} (loss_opr.py:90-92), so the kept
@@ -132,8 +154,7 @@ def test_ohem_selection_bit_exact_given_device_probs(cuda):
     (SURVEY.md section 7), which test_ohem_vs_oracle_fp32 bounds."""
     from torchseg_amd import kernels as K
     kp = K.provider()
-    for (B, C, H, W, regime, frac) in [(2, 19, 128, 128, "confident", 0.5), (1, 19, 512, 512, "confident", 1 / 4),
-                                       (3, 7, 31, 5, "random", 0.9)]:
+    for (B, C, H, W, regime, frac) in shapes:
         pred, t = _make(B, C, H, W, regime, seed=5)
         k = int(B * H * W * frac)
         td = t.to(cuda)

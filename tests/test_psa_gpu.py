@@ -120,7 +120,7 @@ def test_psa_bf16_full_size_fwd_bwd_vs_cpu_oracle(cuda):
 
 
 @pytest.mark.parametrize("regime", ["one_hot_column", "all_large", "all_very_negative"])
-def test_psa_bf16_logits_outside_the_optimistic_range_take_the_guarded_path(cuda, regime):
+def test_psa_bf16_logits_outside_the_optimistic_range_take_the_guarded_path(cuda, regime, shape=(2, 512, 264, 200)):
     """Round 4: the bf16 forward contracts X with exp(A) and normalises by the column sums it collected on the way (no
     column-statistics pass).  That is only safe while a column's sum of exp stays in [1e-20, 1e20]; any tile that sees
     more raises a device flag and the classic three launches (column statistics, exp(a - lse)) redo the call.  Logits far
@@ -129,11 +129,11 @@ def test_psa_bf16_logits_outside_the_optimistic_range_take_the_guarded_path(cuda
     from torchseg_amd import kernels as K
     from torchseg_amd.psa import psa_attention
     g = torch.Generator().manual_seed(5)
-    B, Cx, Kd, N = 2, 512, 264, 200
+    B, Cx, Kd, N = shape
     X = torch.relu(torch.randn(B, Cx, Kd, generator=g)).bfloat16()
     A = torch.randn(B, Kd, N, generator=g) * 2
     if regime == "one_hot_column":
-        A[1, 7, 131] = 120.0                                # exp(120) overflows fp32: one column of one sample
+        A[B - 1, 7, 131] = 120.0                                # exp(120) overflows fp32: one column of one sample
     elif regime == "all_large":
         A = A * 40.0
     else:

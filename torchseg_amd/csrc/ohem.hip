@@ -502,6 +502,8 @@ __global__ __launch_bounds__(kT) void ohem_finish(
     sel[5] = st->n_bad;
     // denominator as float for the backward pass
     reinterpret_cast<float*>(sel)[4] = (float)st->wsum;
+    sel[6] = 0;  // the two spare words of sel[8] (include/tsg_hip.h): written, so the whole tensor is defined
+    sel[7] = 0;
   }
 }
 
