@@ -86,6 +86,24 @@ def test_bn_bf16(cuda, shape, layout, relu, res):
     np.testing.assert_allclose(o["rm"], o["rm_ref"], rtol=1e-4, atol=1e-5)
 
 
+@pytest.mark.parametrize("layout", ["nchw", "nhwc"])
+@pytest.mark.parametrize("res", [False, True])
+def test_bn_bf16_scalar_path_without_relu(cuda, layout, res):
+    """bf16 on the scalar (one element per access) kernels without a ReLU, with and without a residual: 7 x 5 planes (NCHW)
+    and 5 channels (NHWC) are no multiple of the 8-element vector.  Same oracle and bounds as test_bn_bf16."""
+    shape = (2, 5, 7, 5)
+    o = _run(cuda, shape, layout, torch.bfloat16, False, res)
+    n = shape[0] * shape[2] * shape[3]
+    np.testing.assert_allclose(o["y"], o["y_ref"], rtol=8e-3, atol=8e-3)
+    bad = np.abs(o["dx"] - o["dx_ref"]) > (8e-3 + 8e-3 * np.abs(o["dx_ref"]))
+    assert bad.mean() < 1e-3, bad.mean()
+    if res:
+        np.testing.assert_allclose(o["dres"], o["dres_ref"], rtol=0, atol=0)      # no ReLU: the gradient passes unchanged
+    np.testing.assert_allclose(o["dg"], o["dg_ref"], rtol=2e-2, atol=2e-2 * np.sqrt(n))
+    np.testing.assert_allclose(o["db"], o["db_ref"], rtol=2e-2, atol=2e-2 * np.sqrt(n))
+    np.testing.assert_allclose(o["rm"], o["rm_ref"], rtol=1e-4, atol=1e-5)
+
+
 def test_bn_eval_and_errors(cuda):
     from torchseg_amd.syncbn import SyncBatchNorm
     bn = SyncBatchNorm(16).to(cuda)

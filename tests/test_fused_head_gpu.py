@@ -211,3 +211,47 @@ def test_benched_head_bf16_uint8_labels_vs_oracle(cuda, IH, regime):
           "%d pixels in the band, loss %.6f (oracle %.6f), max |ddz| %.3e of %.3e"
           % (B, IH, regime, info["branch"], thr_dev, thr, int(sel[1]), info["n_kept"], perr, n_near, loss.item(),
              ref_loss.item(), err.max().item(), scale))
+
+
+# uint8 labels (ignore value included) through EVERY padded class count of the narrow fused kernels (8, 16, 20, 24, 32), fp32
+# and bf16 logits, at a small head that takes the path: 1 x C x 9 x 9 -> 36 x 36 up to 16 padded classes, -> 72 x 72 above
+# (tsg_ohem_up_supported refuses the x4 head there; the test asserts that the fused path is taken).  Oracle and bounds are
+# the ones used above: oracle.ohem_ref on F.interpolate of the same (bf16-rounded) logits in fp32; fp32 dz as in
+# test_fused_head_vs_oracle_fp32, bf16 dz within one bf16 rounding + the fp32 accumulation order as in
+# test_benched_head_bf16_uint8_labels_vs_oracle.
+@pytest.mark.parametrize("C,S", [(5, 36), (13, 36), (19, 72), (21, 72), (29, 72)])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+def test_fused_head_uint8_labels_every_class_pad(cuda, dtype, C, S):
+    from torchseg_amd import kernels as K
+    from torchseg_amd.losses import ohem_cross_entropy
+    from torchseg_amd.upsample import DeferredUpsample
+    B, IH, IW, OH, OW, thresh = 1, 9, 9, S, S, 0.6
+    z, t = _make(B, C, IH, IW, OH, OW, "confident", seed=100 + C)
+    z = z.to(dtype)
+    min_kept = B * OH * OW // 2
+    assert int((t == 255).sum()) > 0
+    zr = z.float().clone().requires_grad_(True)
+    logits = F.interpolate(zr, size=(OH, OW), mode="bilinear", align_corners=True)
+    ref_loss, info = ohem_ref.ohem_cross_entropy(logits, t, 255, thresh, min_kept, None, return_info=True)
+    ref_loss.backward()
+    zd = z.to(cuda).requires_grad_(True)
+    t8 = t.to(torch.uint8).to(cuda)
+    assert K.provider().ohem_up_supported(zd, OH, OW, thresh)
+    loss, sel = ohem_cross_entropy(DeferredUpsample(zd, (OH, OW)), t8, 255, thresh, min_kept, None, return_selection=True)
+    loss.backward()
+    sel = sel.cpu()
+    assert zd.grad.dtype == dtype
+    assert int(sel[3]) == info["branch"] and int(sel[2]) == info["num_valid"]
+    assert abs(loss.item() - ref_loss.item()) <= 1e-4 * max(1.0, abs(ref_loss.item()))
+    near = 0
+    if info["mask_prob"] is not None:                      # membership may flip only for pixels within ~2 ulp of the threshold
+        near = int((np.abs(info["mask_prob"].numpy() - info["threshold"]) <= 4e-7 * info["threshold"]).sum())
+    assert abs(int(sel[1]) - info["n_kept"]) <= near
+    gref = zr.grad
+    gscale = gref.abs().max().item()
+    err = (zd.grad.float().cpu() - gref).abs()
+    if dtype == torch.float32:
+        assert err.max().item() <= 2e-4 * gscale + (1e-3 * gscale if near else 0.0), (err.max().item(), gscale, near)
+    else:
+        bad = err > gref.abs() * 2.0 ** -7 + 1e-3 * gscale
+        assert int(bad.sum()) <= 4 * C * near, (int(bad.sum()), near, err.max().item(), gscale)

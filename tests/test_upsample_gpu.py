@@ -46,6 +46,30 @@ def test_bilinear_fused_add(cuda):
     torch.testing.assert_close(a.grad, g)
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_bilinear_fused_add_scalar_path(cuda, dtype):
+    """the fused `+ add` on the scalar kernels: 9 output columns are no multiple of the 16-byte vector (2 x 5 x 7 x 5 ->
+    13 x 9).  Oracle and bounds of test_bilinear_fwd_bwd; the addend's gradient is the incoming gradient itself."""
+    from torchseg_amd.upsample import upsample_bilinear_ac
+    g = torch.Generator().manual_seed(59)
+    x = torch.randn(2, 5, 7, 5, generator=g).to(dtype)
+    a = torch.randn(2, 5, 13, 9, generator=g).to(dtype)
+    xd, ad = x.to(cuda).requires_grad_(True), a.to(cuda).requires_grad_(True)
+    y = upsample_bilinear_ac(xd, size=(13, 9), add=ad)
+    assert y.dtype == dtype
+    ref = R.upsample_bilinear_ac(x.float().numpy(), 13, 9) + a.float().numpy()
+    tol = 1e-5 if dtype == torch.float32 else 8e-3
+    np.testing.assert_allclose(y.detach().float().cpu().numpy(), ref, rtol=tol, atol=tol)
+    dy = torch.randn(2, 5, 13, 9, generator=g).to(dtype).to(cuda)
+    y.backward(dy)
+    assert torch.equal(ad.grad, dy)
+    dx_ref = R.upsample_bilinear_ac_backward(dy.float().cpu().numpy(), 7, 5)
+    if dtype == torch.float32:
+        np.testing.assert_allclose(xd.grad.cpu().numpy(), dx_ref, rtol=1e-4, atol=1e-4 * max(1.0, 13 / 7))
+    else:
+        np.testing.assert_allclose(xd.grad.float().cpu().numpy(), dx_ref, rtol=1e-2, atol=1e-2 * np.abs(dx_ref).max())
+
+
 def test_adjointness_full_size(cuda):
     """config-2 head size 19 x 128^2 -> 1024^2: <up(x), g> == <x, up^T(g)>."""
     from torchseg_amd import kernels as K

@@ -18,7 +18,7 @@
 //   apply_fwd    1 read + 1 write  = 2s   (+s with residual)
 //   bwd_reduce   2 reads           = 2s   (+s when the ReLU mask comes from y)
 //   bwd_apply    2 reads + 1 write = 3s   (+s mask-from-y, +s dres)
-#include "tsg_common.h"
+#include "tsg_dispatch.h"
 
 namespace tsg {
 
@@ -89,7 +89,7 @@ static NhwcGeom nhwc_geom(int64_t M, int64_t C, int V) {
 
 static int pick_vec(int dtype, int layout, int64_t C, int64_t HW, const void* p0,
                     const void* p1, const void* p2, const void* p3, const void* p4) {
-  const int native = (dtype == TSG_BF16) ? 8 : 4;
+  const int native = native_vec(dtype);
   const int64_t inner = (layout == TSG_NCHW) ? HW : C;
   if (inner % native != 0) return 1;
   const void* ps[5] = {p0, p1, p2, p3, p4};
@@ -810,50 +810,45 @@ template <typename T, int V, int MODE>
 static int launch_reduce(const T* x, const T* dy, const T* y, int layout, int64_t N,
                          int64_t C, int64_t HW, const float* fp, int mask,
                          float* partial, hipStream_t st) {
-  if (layout == TSG_NCHW) {
-    NchwGeom g = nchw_geom(N, C, HW, V);
-    dim3 grid((unsigned)C, (unsigned)g.split);
-#define L_(MK) hipLaunchKernelGGL((bn_reduce_nchw<T, V, MODE, MK>), grid, dim3(kThreads), 0, st, \
-      x, dy, y, N, C, HW, g.seg, g.segs, g.split, fp, partial)
-    if (MODE == 0 || mask == 0) L_(0); else if (mask == 1) L_(1); else L_(2);
-#undef L_
-  } else {
-    const int64_t M = N * HW;
-    NhwcGeom g = nhwc_geom(M, C, V);
-    dim3 grid((unsigned)g.split, (unsigned)g.ytiles);
-    const size_t sh = (size_t)2 * g.rows_per_iter * g.gt * V * sizeof(typename RedAcc<T, MODE>::type);
-#define L_(MK) hipLaunchKernelGGL((bn_reduce_nhwc<T, V, MODE, MK>), grid, dim3(kThreads), sh, st, \
-      x, dy, y, M, C, g.gt, g.rows_per_iter, g.rows_per_block, fp, partial)
-    if (MODE == 0 || mask == 0) L_(0); else if (mask == 1) L_(1); else L_(2);
-#undef L_
-  }
-  TSG_CHECK_LAUNCH();
-  return 0;
+  return with_int<0, 1, 2>(MODE == 0 ? 0 : mask, [&](auto mk) {
+    if (layout == TSG_NCHW) {
+      NchwGeom g = nchw_geom(N, C, HW, V);
+      dim3 grid((unsigned)C, (unsigned)g.split);
+      hipLaunchKernelGGL((bn_reduce_nchw<T, V, MODE, mk()>), grid, dim3(kThreads), 0, st, x, dy, y, N, C, HW, g.seg, g.segs,
+                         g.split, fp, partial);
+    } else {
+      const int64_t M = N * HW;
+      NhwcGeom g = nhwc_geom(M, C, V);
+      dim3 grid((unsigned)g.split, (unsigned)g.ytiles);
+      const size_t sh = (size_t)2 * g.rows_per_iter * g.gt * V * sizeof(typename RedAcc<T, MODE>::type);
+      hipLaunchKernelGGL((bn_reduce_nhwc<T, V, MODE, mk()>), grid, dim3(kThreads), sh, st, x, dy, y, M, C, g.gt,
+                         g.rows_per_iter, g.rows_per_block, fp, partial);
+    }
+    TSG_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 template <typename T, int V>
 static int launch_fwd(const T* x, const T* res, T* y, int layout, int64_t N, int64_t C,
                       int64_t HW, const float* fp, int relu, hipStream_t st) {
-  const bool R_ = relu != 0, S_ = res != nullptr;
-  if (layout == TSG_NCHW) {
-    NchwGeom g = nchw_geom(N, C, HW, V);
-    const int64_t blocks = N * C * g.segs;
-    if (blocks > 0x7fffffffLL) return TSG_E_SHAPE;
-#define L_(A, B) hipLaunchKernelGGL((bn_fwd_nchw<T, V, A, B>), dim3((unsigned)blocks), dim3(kThreads), 0, st, \
-      x, res, y, C, HW, g.seg, g.segs, fp)
-    if (R_ && S_) L_(true, true); else if (R_) L_(true, false); else if (S_) L_(false, true); else L_(false, false);
-#undef L_
-  } else {
-    const int64_t M = N * HW;
-    NhwcGeom g = nhwc_geom(M, C, V);
-    dim3 grid((unsigned)g.split, (unsigned)g.ytiles);
-#define L_(A, B) hipLaunchKernelGGL((bn_fwd_nhwc<T, V, A, B>), grid, dim3(kThreads), 0, st, \
-      x, res, y, M, C, g.gt, g.rows_per_iter, g.rows_per_block, fp, bn_reverse())
-    if (R_ && S_) L_(true, true); else if (R_) L_(true, false); else if (S_) L_(false, true); else L_(false, false);
-#undef L_
-  }
-  TSG_CHECK_LAUNCH();
-  return 0;
+  return with_flag(relu != 0, [&](auto r) { return with_flag(res != nullptr, [&](auto s) {
+    if (layout == TSG_NCHW) {
+      NchwGeom g = nchw_geom(N, C, HW, V);
+      const int64_t blocks = N * C * g.segs;
+      if (blocks > 0x7fffffffLL) return TSG_E_SHAPE;
+      hipLaunchKernelGGL((bn_fwd_nchw<T, V, r(), s()>), dim3((unsigned)blocks), dim3(kThreads), 0, st, x, res, y, C, HW,
+                         g.seg, g.segs, fp);
+    } else {
+      const int64_t M = N * HW;
+      NhwcGeom g = nhwc_geom(M, C, V);
+      dim3 grid((unsigned)g.split, (unsigned)g.ytiles);
+      hipLaunchKernelGGL((bn_fwd_nhwc<T, V, r(), s()>), grid, dim3(kThreads), 0, st, x, res, y, M, C, g.gt, g.rows_per_iter,
+                         g.rows_per_block, fp, bn_reverse());
+    }
+    TSG_CHECK_LAUNCH();
+    return 0;
+  }); });
 }
 
 // the bit-mask forms (NHWC, V = 8 bf16 / 4 fp32 channels per byte): forward of BN -> (+identity) -> ReLU that also writes
@@ -864,14 +859,12 @@ static int launch_fwd_bits(const T* x, const T* res, T* y, unsigned char* bits, 
   const int64_t M = N * HW;
   NhwcGeom g = nhwc_geom(M, C, V);
   dim3 grid((unsigned)g.split, (unsigned)g.ytiles);
-  if (res)
-    hipLaunchKernelGGL((bn_fwd_nhwc<T, V, true, true, true>), grid, dim3(kThreads), 0, st, x, res, y, M, C, g.gt,
+  return with_flag(res != nullptr, [&](auto s) {
+    hipLaunchKernelGGL((bn_fwd_nhwc<T, V, true, s(), true>), grid, dim3(kThreads), 0, st, x, res, y, M, C, g.gt,
                        g.rows_per_iter, g.rows_per_block, fp, bn_reverse(), bits);
-  else
-    hipLaunchKernelGGL((bn_fwd_nhwc<T, V, true, false, true>), grid, dim3(kThreads), 0, st, x, res, y, M, C, g.gt,
-                       g.rows_per_iter, g.rows_per_block, fp, bn_reverse(), bits);
-  TSG_CHECK_LAUNCH();
-  return 0;
+    TSG_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 template <typename T, int V>
@@ -893,41 +886,34 @@ static int launch_bwd_bits(const T* dy, const T* x, const unsigned char* bits, T
   const int64_t M = N * HW;
   NhwcGeom g = nhwc_geom(M, C, V);
   dim3 grid((unsigned)g.split, (unsigned)g.ytiles);
-#define L_(D) hipLaunchKernelGGL((bn_bwd_nhwc<T, V, 3, D>), grid, dim3(kThreads), 0, st, dy, x, reinterpret_cast<const T*>(bits), \
-      dx, dres, M, C, g.gt, g.rows_per_iter, g.rows_per_block, bp, bn_reverse())
-  if (dres) L_(true); else L_(false);
-#undef L_
-  TSG_CHECK_LAUNCH();
-  return 0;
+  return with_flag(dres != nullptr, [&](auto d) {
+    hipLaunchKernelGGL((bn_bwd_nhwc<T, V, 3, d()>), grid, dim3(kThreads), 0, st, dy, x, reinterpret_cast<const T*>(bits), dx,
+                       dres, M, C, g.gt, g.rows_per_iter, g.rows_per_block, bp, bn_reverse());
+    TSG_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 template <typename T, int V>
 static int launch_bwd(const T* dy, const T* x, const T* y, T* dx, T* dres, int layout,
                       int64_t N, int64_t C, int64_t HW, const float* bp, int mask, hipStream_t st) {
-  const bool D_ = dres != nullptr;
-  if (layout == TSG_NCHW) {
-    NchwGeom g = nchw_geom(N, C, HW, V);
-    const int64_t blocks = N * C * g.segs;
-    if (blocks > 0x7fffffffLL) return TSG_E_SHAPE;
-#define L_(MK, D) hipLaunchKernelGGL((bn_bwd_nchw<T, V, MK, D>), dim3((unsigned)blocks), dim3(kThreads), 0, st, \
-      dy, x, y, dx, dres, C, HW, g.seg, g.segs, bp)
-    if (mask == 0) { if (D_) L_(0, true); else L_(0, false); }
-    else if (mask == 1) { if (D_) L_(1, true); else L_(1, false); }
-    else { if (D_) L_(2, true); else L_(2, false); }
-#undef L_
-  } else {
-    const int64_t M = N * HW;
-    NhwcGeom g = nhwc_geom(M, C, V);
-    dim3 grid((unsigned)g.split, (unsigned)g.ytiles);
-#define L_(MK, D) hipLaunchKernelGGL((bn_bwd_nhwc<T, V, MK, D>), grid, dim3(kThreads), 0, st, \
-      dy, x, y, dx, dres, M, C, g.gt, g.rows_per_iter, g.rows_per_block, bp, bn_reverse())
-    if (mask == 0) { if (D_) L_(0, true); else L_(0, false); }
-    else if (mask == 1) { if (D_) L_(1, true); else L_(1, false); }
-    else { if (D_) L_(2, true); else L_(2, false); }
-#undef L_
-  }
-  TSG_CHECK_LAUNCH();
-  return 0;
+  return with_int<0, 1, 2>(mask, [&](auto mk) { return with_flag(dres != nullptr, [&](auto d) {
+    if (layout == TSG_NCHW) {
+      NchwGeom g = nchw_geom(N, C, HW, V);
+      const int64_t blocks = N * C * g.segs;
+      if (blocks > 0x7fffffffLL) return TSG_E_SHAPE;
+      hipLaunchKernelGGL((bn_bwd_nchw<T, V, mk(), d()>), dim3((unsigned)blocks), dim3(kThreads), 0, st, dy, x, y, dx, dres, C,
+                         HW, g.seg, g.segs, bp);
+    } else {
+      const int64_t M = N * HW;
+      NhwcGeom g = nhwc_geom(M, C, V);
+      dim3 grid((unsigned)g.split, (unsigned)g.ytiles);
+      hipLaunchKernelGGL((bn_bwd_nhwc<T, V, mk(), d()>), grid, dim3(kThreads), 0, st, dy, x, y, dx, dres, M, C, g.gt,
+                         g.rows_per_iter, g.rows_per_block, bp, bn_reverse());
+    }
+    TSG_CHECK_LAUNCH();
+    return 0;
+  }); });
 }
 
 static int check_dims(int dtype, int layout, int64_t N, int64_t C, int64_t HW) {
@@ -950,14 +936,11 @@ static int bn_reduce_dispatch(int mode, const void* x, const void* dy, const voi
   hipStream_t st = (hipStream_t)stream;
   const int V = pick_vec(dtype, layout, C, HW, x, dy, mask == 1 ? y : nullptr, nullptr, nullptr);
   *rows = partial_rows(layout, N, C, HW, V) * (dtype == TSG_F32 ? 2 : 1);   // fp32 tensors: fp64 sums as hi + lo rows
-#define GO(T, VV)                                                                          \
-  (mode == 0 ? launch_reduce<T, VV, 0>((const T*)x, nullptr, nullptr, layout, N, C, HW,    \
-                                       fp, 0, partial, st)                                 \
-             : launch_reduce<T, VV, 1>((const T*)x, (const T*)dy, (const T*)y, layout, N,  \
-                                       C, HW, fp, mask, partial, st))
-  if (dtype == TSG_F32) return V == 4 ? GO(float, 4) : GO(float, 1);
-  return V == 8 ? GO(bf16_t, 8) : GO(bf16_t, 1);
-#undef GO
+  return with_elem_vec(dtype, V != 1, [&](auto t, auto v) {
+    typedef typename decltype(t)::type T;
+    return mode == 0 ? launch_reduce<T, v(), 0>((const T*)x, nullptr, nullptr, layout, N, C, HW, fp, 0, partial, st)
+                     : launch_reduce<T, v(), 1>((const T*)x, (const T*)dy, (const T*)y, layout, N, C, HW, fp, mask, partial, st);
+  });
 }
 
 }  // namespace tsg
@@ -1047,10 +1030,10 @@ int tsg_bn_apply_fwd(const void* x, const void* residual, void* y, int dtype, in
   if (!aligned16(fwd_pack)) return TSG_E_ALIGN;
   hipStream_t st = (hipStream_t)stream;
   const int V = pick_vec(dtype, layout, C, HW, x, residual, y, nullptr, nullptr);
-#define GO(T, VV) launch_fwd<T, VV>((const T*)x, (const T*)residual, (T*)y, layout, N, C, HW, fwd_pack, relu, st)
-  if (dtype == TSG_F32) return V == 4 ? GO(float, 4) : GO(float, 1);
-  return V == 8 ? GO(bf16_t, 8) : GO(bf16_t, 1);
-#undef GO
+  return with_elem_vec(dtype, V != 1, [&](auto t, auto v) {
+    typedef typename decltype(t)::type T;
+    return launch_fwd<T, v()>((const T*)x, (const T*)residual, (T*)y, layout, N, C, HW, fwd_pack, relu, st);
+  });
 }
 
 int tsg_bn_bwd_reduce(const void* dy, const void* x, const void* y, int dtype, int layout,
@@ -1086,11 +1069,10 @@ int tsg_bn_bwd_apply(const void* dy, const void* x, const void* y, void* dx, voi
   hipStream_t st = (hipStream_t)stream;
   const int mask = relu ? (y ? 1 : 2) : 0;
   const int V = pick_vec(dtype, layout, C, HW, x, dy, mask == 1 ? y : nullptr, dx, dres);
-#define GO(T, VV) launch_bwd<T, VV>((const T*)dy, (const T*)x, (const T*)y, (T*)dx, (T*)dres, \
-                                    layout, N, C, HW, bwd_pack, mask, st)
-  if (dtype == TSG_F32) return V == 4 ? GO(float, 4) : GO(float, 1);
-  return V == 8 ? GO(bf16_t, 8) : GO(bf16_t, 1);
-#undef GO
+  return with_elem_vec(dtype, V != 1, [&](auto t, auto v) {
+    typedef typename decltype(t)::type T;
+    return launch_bwd<T, v()>((const T*)dy, (const T*)x, (const T*)y, (T*)dx, (T*)dres, layout, N, C, HW, bwd_pack, mask, st);
+  });
 }
 
 // ---- ReLU mask as one bit per element (block tails: BN -> (+identity) -> ReLU) --------------------------------
@@ -1151,7 +1133,7 @@ int tsg_bn_bwd_apply_maskbits(const void* dy, const void* x, const void* bits, v
 
 // ---- mixed layout (x NCHW, y/dy NHWC) --------------------------------------------
 static int mixed_ok(int dtype, int64_t C, int64_t HW) {
-  const int V = dtype == TSG_BF16 ? 8 : 4;
+  const int V = native_vec(dtype);
   return (dtype == TSG_F32 || dtype == TSG_BF16) && C % 8 == 0 && C <= 128 && HW % V == 0;
 }
 
@@ -1177,13 +1159,12 @@ int tsg_bn_apply_fwd_mixed(const void* x_nchw, void* y_nhwc, int dtype, int64_t 
   const size_t sh = (size_t)kTP * (C + 1) * sizeof(float);
   dim3 grid((unsigned)(N * tpi));
   hipStream_t st = (hipStream_t)stream;
-#define GO(T, R) hipLaunchKernelGGL((bn_fwd_mixed<T, R>), grid, dim3(kThreads), sh, st, (const T*)x_nchw, \
-                                    (T*)y_nhwc, C, HW, tpi, fwd_pack)
-  if (dtype == TSG_F32) { if (relu) GO(float, true); else GO(float, false); }
-  else { if (relu) GO(bf16_t, true); else GO(bf16_t, false); }
-#undef GO
-  TSG_CHECK_LAUNCH();
-  return 0;
+  return with_elem(dtype, [&](auto t) { return with_flag(relu != 0, [&](auto r) {
+    typedef typename decltype(t)::type T;
+    hipLaunchKernelGGL((bn_fwd_mixed<T, r()>), grid, dim3(kThreads), sh, st, (const T*)x_nchw, (T*)y_nhwc, C, HW, tpi, fwd_pack);
+    TSG_CHECK_LAUNCH();
+    return 0;
+  }); });
 }
 
 int tsg_bn_bwd_reduce_mixed(const void* dy_nhwc, const void* x_nchw, int dtype, int64_t N, int64_t C,
@@ -1194,7 +1175,7 @@ int tsg_bn_bwd_reduce_mixed(const void* dy_nhwc, const void* x_nchw, int dtype, 
   if (!aligned16(x_nchw) || !aligned16(dy_nhwc)) return TSG_E_ALIGN;
   const int tpi = (int)((HW + kTP - 1) / kTP);
   const int64_t total = N * tpi;
-  const int V = dtype == TSG_BF16 ? 8 : 4;
+  const int V = native_vec(dtype);
   size_t sh = (size_t)kTP * (C + 1) * sizeof(float);
   const size_t red = (size_t)2 * C * (kTP / V) * sizeof(float);
   if (red > sh) sh = red;
@@ -1202,16 +1183,14 @@ int tsg_bn_bwd_reduce_mixed(const void* dy_nhwc, const void* x_nchw, int dtype, 
   if (rows) *rows = blocks;
   hipStream_t st = (hipStream_t)stream;
   const int items = (int)((C * (kTP / V) + kThreads - 1) / kThreads);   // 1..8 for C <= 128
-#define GO(T, R, I) hipLaunchKernelGGL((bn_bwd_reduce_mixed<T, R, I>), dim3(blocks), dim3(kThreads), sh, st, \
-                                       (const T*)dy_nhwc, (const T*)x_nchw, C, HW, tpi, total, fwd_pack, partial)
-#define GI(T, R) do { if (items <= 1) GO(T, R, 1); else if (items <= 2) GO(T, R, 2); else if (items <= 4) GO(T, R, 4); \
-                      else GO(T, R, 8); } while (0)
-  if (dtype == TSG_F32) { if (relu) GI(float, true); else GI(float, false); }
-  else { if (relu) GI(bf16_t, true); else GI(bf16_t, false); }
-#undef GI
-#undef GO
-  TSG_CHECK_LAUNCH();
-  return 0;
+  const int ipt = items <= 1 ? 1 : items <= 2 ? 2 : items <= 4 ? 4 : 8;  // items per thread the kernel is built for
+  return with_elem(dtype, [&](auto t) { return with_flag(relu != 0, [&](auto r) { return with_int<1, 2, 4, 8>(ipt, [&](auto i) {
+    typedef typename decltype(t)::type T;
+    hipLaunchKernelGGL((bn_bwd_reduce_mixed<T, r(), i()>), dim3(blocks), dim3(kThreads), sh, st, (const T*)dy_nhwc,
+                       (const T*)x_nchw, C, HW, tpi, total, fwd_pack, partial);
+    TSG_CHECK_LAUNCH();
+    return 0;
+  }); }); });
 }
 
 int tsg_bn_bwd_apply_mixed(const void* dy_nhwc, const void* x_nchw, void* dx_nchw, int dtype, int64_t N,
@@ -1223,13 +1202,13 @@ int tsg_bn_bwd_apply_mixed(const void* dy_nhwc, const void* x_nchw, void* dx_nch
   const size_t sh = (size_t)kTP * (C + 1) * sizeof(float);
   dim3 grid((unsigned)(N * tpi));
   hipStream_t st = (hipStream_t)stream;
-#define GO(T, R) hipLaunchKernelGGL((bn_bwd_apply_mixed<T, R>), grid, dim3(kThreads), sh, st, \
-                                    (const T*)dy_nhwc, (const T*)x_nchw, (T*)dx_nchw, C, HW, tpi, bwd_pack)
-  if (dtype == TSG_F32) { if (relu) GO(float, true); else GO(float, false); }
-  else { if (relu) GO(bf16_t, true); else GO(bf16_t, false); }
-#undef GO
-  TSG_CHECK_LAUNCH();
-  return 0;
+  return with_elem(dtype, [&](auto t) { return with_flag(relu != 0, [&](auto r) {
+    typedef typename decltype(t)::type T;
+    hipLaunchKernelGGL((bn_bwd_apply_mixed<T, r()>), grid, dim3(kThreads), sh, st, (const T*)dy_nhwc, (const T*)x_nchw,
+                       (T*)dx_nchw, C, HW, tpi, bwd_pack);
+    TSG_CHECK_LAUNCH();
+    return 0;
+  }); });
 }
 
 }  // extern "C"

@@ -11,7 +11,7 @@
 //             (sum dy', sum dy' (x - mean)) and, in the second pass, by dx = a dy' + Bc (x - mean) + C2.
 // HBM per element of x (s = element size): forward s + (s + 1) / 4; backward 2 s + s (+ the pooled side arrays, 1/4 size).
 // Packs as in bn.hip: fp[3][C] = {a, b, mean}, bp[5][C] = {a, b, mean, Bc, C2}; partial[S][2][C] fp32.
-#include "tsg_common.h"
+#include "tsg_dispatch.h"
 
 namespace tsg {
 
@@ -312,7 +312,7 @@ __global__ __launch_bounds__(kBpT) void bn_relu_pool_bwd_apply_k(
 
 static int bp_check(int dtype, int64_t N, int C, int IH, int IW, int OH, int OW) {
   if (dtype != TSG_F32 && dtype != TSG_BF16) return TSG_E_DTYPE;
-  const int V = dtype == TSG_BF16 ? 8 : 4;
+  const int V = native_vec(dtype);
   if (N <= 0 || C <= 0 || C % V || IH <= 0 || IW <= 0) return TSG_E_SHAPE;
   if (OH != (IH - 1) / 2 + 1 || OW != (IW - 1) / 2 + 1) return TSG_E_SHAPE;       // K = 3, S = 2, P = 1
   return 0;
@@ -331,20 +331,19 @@ int tsg_bn_relu_pool_fwd(const void* x, void* y, void* argmax_u8, int dtype, int
   if (e) return e;
   if (!aligned16(x) || !aligned16(y) || !aligned16(fp) || (((uintptr_t)argmax_u8) & 7u)) return TSG_E_ALIGN;
   hipStream_t st = (hipStream_t)stream;
-  const int V = dtype == TSG_BF16 ? 8 : 4;
+  const int V = native_vec(dtype);
   const BpMap m = bp_map(C, V);
   const int ytiles = (C / V + m.GT - 1) / m.GT;
   const int64_t gy = (int64_t)((OH + kFwdRows - 1) / kFwdRows) * ytiles;
   if (gy > 65535 || N > 65535) return TSG_E_SHAPE;
   dim3 grid((unsigned)((OW + m.PW - 1) / m.PW), (unsigned)gy, (unsigned)N);
-  if (dtype == TSG_BF16)
-    hipLaunchKernelGGL((bn_relu_pool_fwd_k<bf16_t>), grid, dim3(kBpT), 0, st, (const bf16_t*)x, (bf16_t*)y,
-                       (uint8_t*)argmax_u8, C, IH, IW, OH, OW, m.GT, m.PW, ytiles, fp);
-  else
-    hipLaunchKernelGGL((bn_relu_pool_fwd_k<float>), grid, dim3(kBpT), 0, st, (const float*)x, (float*)y,
-                       (uint8_t*)argmax_u8, C, IH, IW, OH, OW, m.GT, m.PW, ytiles, fp);
-  TSG_CHECK_LAUNCH();
-  return 0;
+  return with_elem(dtype, [&](auto t) {
+    typedef typename decltype(t)::type T;
+    hipLaunchKernelGGL((bn_relu_pool_fwd_k<T>), grid, dim3(kBpT), 0, st, (const T*)x, (T*)y, (uint8_t*)argmax_u8, C, IH, IW, OH,
+                       OW, m.GT, m.PW, ytiles, fp);
+    TSG_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 struct BpRed { BpMap m; int ytiles, rows, chunks; int64_t S; };
@@ -361,7 +360,7 @@ static BpRed bp_red(int64_t N, int C, int IH, int IW, int V) {
 
 int tsg_bn_relu_pool_bwd_num_partials(int dtype, int64_t N, int C, int IH, int IW) {
   if (dtype != TSG_F32 && dtype != TSG_BF16) return TSG_E_DTYPE;
-  const int V = dtype == TSG_BF16 ? 8 : 4;
+  const int V = native_vec(dtype);
   if (N <= 0 || C <= 0 || C % V || IH <= 0 || IW <= 0) return TSG_E_SHAPE;
   const BpRed r = bp_red(N, C, IH, IW, V);
   if (r.S > 0x7fffffffLL) return TSG_E_SHAPE;
@@ -375,22 +374,19 @@ int tsg_bn_relu_pool_bwd_reduce(const void* dpool, const void* argmax_u8, const 
   if (e) return e;
   if (!aligned16(x) || !aligned16(dpool) || !aligned16(fp) || (((uintptr_t)argmax_u8) & 7u)) return TSG_E_ALIGN;
   hipStream_t st = (hipStream_t)stream;
-  const int V = dtype == TSG_BF16 ? 8 : 4;
+  const int V = native_vec(dtype);
   const BpRed r = bp_red(N, C, IH, IW, V);
   const int64_t gy = (int64_t)r.chunks * r.ytiles;
   if (gy > 65535 || N > 65535) return TSG_E_SHAPE;
   dim3 grid((unsigned)(((IW + 1) / 2 + r.m.PW - 1) / r.m.PW), (unsigned)gy, (unsigned)N);
   const size_t sh = (size_t)2 * r.m.PW * r.m.GT * V * sizeof(float);
-  if (dtype == TSG_BF16)
-    hipLaunchKernelGGL((bn_relu_pool_bwd_reduce_k<bf16_t>), grid, dim3(kBpT), sh, st, (const bf16_t*)dpool,
-                       (const uint8_t*)argmax_u8, (const bf16_t*)x, C, IH, IW, OH, OW, r.m.GT, r.m.PW, r.ytiles, r.rows,
-                       fp, partial);
-  else
-    hipLaunchKernelGGL((bn_relu_pool_bwd_reduce_k<float>), grid, dim3(kBpT), sh, st, (const float*)dpool,
-                       (const uint8_t*)argmax_u8, (const float*)x, C, IH, IW, OH, OW, r.m.GT, r.m.PW, r.ytiles, r.rows,
-                       fp, partial);
-  TSG_CHECK_LAUNCH();
-  return 0;
+  return with_elem(dtype, [&](auto t) {
+    typedef typename decltype(t)::type T;
+    hipLaunchKernelGGL((bn_relu_pool_bwd_reduce_k<T>), grid, dim3(kBpT), sh, st, (const T*)dpool, (const uint8_t*)argmax_u8,
+                       (const T*)x, C, IH, IW, OH, OW, r.m.GT, r.m.PW, r.ytiles, r.rows, fp, partial);
+    TSG_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 int tsg_bn_relu_pool_bwd_apply(const void* dpool, const void* argmax_u8, const void* x, void* dx, int dtype, int64_t N,
@@ -401,20 +397,19 @@ int tsg_bn_relu_pool_bwd_apply(const void* dpool, const void* argmax_u8, const v
   if (!aligned16(x) || !aligned16(dx) || !aligned16(dpool) || !aligned16(bp) || (((uintptr_t)argmax_u8) & 7u))
     return TSG_E_ALIGN;
   hipStream_t st = (hipStream_t)stream;
-  const int V = dtype == TSG_BF16 ? 8 : 4;
+  const int V = native_vec(dtype);
   const BpMap m = bp_map(C, V);
   const int ytiles = (C / V + m.GT - 1) / m.GT;
   const int64_t gy = (int64_t)(((IH + 1) / 2 + kAppRows - 1) / kAppRows) * ytiles;
   if (gy > 65535 || N > 65535) return TSG_E_SHAPE;
   dim3 grid((unsigned)(((IW + 1) / 2 + m.PW - 1) / m.PW), (unsigned)gy, (unsigned)N);
-  if (dtype == TSG_BF16)
-    hipLaunchKernelGGL((bn_relu_pool_bwd_apply_k<bf16_t>), grid, dim3(kBpT), 0, st, (const bf16_t*)dpool,
-                       (const uint8_t*)argmax_u8, (const bf16_t*)x, (bf16_t*)dx, C, IH, IW, OH, OW, m.GT, m.PW, ytiles, bp);
-  else
-    hipLaunchKernelGGL((bn_relu_pool_bwd_apply_k<float>), grid, dim3(kBpT), 0, st, (const float*)dpool,
-                       (const uint8_t*)argmax_u8, (const float*)x, (float*)dx, C, IH, IW, OH, OW, m.GT, m.PW, ytiles, bp);
-  TSG_CHECK_LAUNCH();
-  return 0;
+  return with_elem(dtype, [&](auto t) {
+    typedef typename decltype(t)::type T;
+    hipLaunchKernelGGL((bn_relu_pool_bwd_apply_k<T>), grid, dim3(kBpT), 0, st, (const T*)dpool, (const uint8_t*)argmax_u8,
+                       (const T*)x, (T*)dx, C, IH, IW, OH, OW, m.GT, m.PW, ytiles, bp);
+    TSG_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 }  // extern "C"

@@ -18,6 +18,7 @@
 //                                                                      fixed order; dbias[n] = sum dz by a plane-sum kernel
 // All three are HBM-bound (x / dx once).  n_classes <= 32, C_in in {32, 64, 128, 256}, H*W a multiple of 16.
 #include "tsg_mfma.h"
+#include "tsg_dispatch.h"
 
 namespace tsg {
 
@@ -281,15 +282,11 @@ int tsg_cls_head_fwd(const void* x, const float* w, const float* bias, void* z, 
   int64_t blocks = (ngroups + 3) / 4;
   if (blocks > 2048) blocks = 2048;
   hipStream_t st = (hipStream_t)stream;
-#define CH_F(KS) hipLaunchKernelGGL((cls_fwd_k<KS>), dim3((unsigned)blocks), dim3(256), 0, st, (const bf16_t*)x, w, bias, (bf16_t*)z, g)
-  switch (Cin / 16) {
-    case 1: CH_F(1); break; case 2: CH_F(2); break; case 4: CH_F(4); break; case 8: CH_F(8); break;
-    case 16: CH_F(16); break;
-    default: return TSG_E_SHAPE;
-  }
-#undef CH_F
-  TSG_CHECK_LAUNCH();
-  return 0;
+  return with_int<1, 2, 4, 8, 16>(Cin / 16, [&](auto ks) {
+    hipLaunchKernelGGL((cls_fwd_k<ks()>), dim3((unsigned)blocks), dim3(256), 0, st, (const bf16_t*)x, w, bias, (bf16_t*)z, g);
+    TSG_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 int tsg_cls_head_dgrad(const void* dz, const float* w, void* dx, int64_t B, int64_t HW, int Cin, int n_classes, void* stream) {
@@ -302,14 +299,11 @@ int tsg_cls_head_dgrad(const void* dz, const float* w, void* dx, int64_t B, int6
   int64_t blocks = (ngroups + 3) / 4;
   if (blocks > 1024) blocks = 1024;
   hipStream_t st = (hipStream_t)stream;
-#define CH_D(CT) hipLaunchKernelGGL((cls_dgrad_k<CT>), dim3((unsigned)blocks), dim3(256), 0, st, (const bf16_t*)dz, w, (bf16_t*)dx, g)
-  switch (Cin / 32) {
-    case 1: CH_D(1); break; case 2: CH_D(2); break; case 4: CH_D(4); break; case 8: CH_D(8); break;
-    default: return TSG_E_SHAPE;
-  }
-#undef CH_D
-  TSG_CHECK_LAUNCH();
-  return 0;
+  return with_int<1, 2, 4, 8>(Cin / 32, [&](auto ct) {
+    hipLaunchKernelGGL((cls_dgrad_k<ct()>), dim3((unsigned)blocks), dim3(256), 0, st, (const bf16_t*)dz, w, (bf16_t*)dx, g);
+    TSG_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 size_t tsg_cls_head_wgrad_ws_bytes(int64_t B, int Cin, int n_classes) {
@@ -330,13 +324,12 @@ int tsg_cls_head_wgrad(const void* dz, const void* x, float* dw, float* dbias, i
   float* part = (float*)ws;
   float* part_b = part + (size_t)CH_WBLOCKS * n_classes * Cin;
   hipStream_t st = (hipStream_t)stream;
-#define CH_W(CT) hipLaunchKernelGGL((cls_wgrad_k<CT>), dim3((unsigned)blocks), dim3(256), 0, st, (const bf16_t*)dz, (const bf16_t*)x, part, g)
-  switch (Cin / 32) {
-    case 1: CH_W(1); break; case 2: CH_W(2); break; case 4: CH_W(4); break; case 8: CH_W(8); break;
-    default: return TSG_E_SHAPE;
-  }
-#undef CH_W
-  TSG_CHECK_LAUNCH();
+  e = with_int<1, 2, 4, 8>(Cin / 32, [&](auto ct) {
+    hipLaunchKernelGGL((cls_wgrad_k<ct()>), dim3((unsigned)blocks), dim3(256), 0, st, (const bf16_t*)dz, (const bf16_t*)x, part, g);
+    TSG_CHECK_LAUNCH();
+    return 0;
+  });
+  if (e) return e;
   if (dbias) {
     hipLaunchKernelGGL(cls_dbias_k, dim3((unsigned)n_classes, (unsigned)B), dim3(256), 0, st, (const bf16_t*)dz, part_b, g);
     TSG_CHECK_LAUNCH();

@@ -9,7 +9,7 @@
 //   loss = mean over ALL pixels of -(alpha*pos + (1-alpha)*neg) * m
 // The reference spends ~15 element-wise temporaries; here: one read of
 // (pred, target) forward, one read + one write backward.  HBM-bound.
-#include "tsg_common.h"
+#include "tsg_dispatch.h"
 #include <math.h>
 
 namespace tsg {
@@ -98,16 +98,14 @@ int tsg_focal_fwd(const void* pred, int dtype, const void* target, int ltype, in
   hipStream_t st = (hipStream_t)stream;
   const int grid = fgrid(P);
   const float ig = (float)ignore_label;
-#define GO(T, LT) hipLaunchKernelGGL((focal_fwd_k<T, LT>), dim3(grid), dim3(kT), 0, st, (const T*)pred, \
-                                     target, P, ig, gamma, alpha, (float*)ws)
-  if (dtype == TSG_F32) { if (ltype == TSG_I64) GO(float, TSG_I64); else if (ltype == TSG_U8) GO(float, TSG_U8); else return TSG_E_DTYPE; }
-  else if (dtype == TSG_BF16) { if (ltype == TSG_I64) GO(bf16_t, TSG_I64); else if (ltype == TSG_U8) GO(bf16_t, TSG_U8); else return TSG_E_DTYPE; }
-  else return TSG_E_DTYPE;
-#undef GO
-  TSG_CHECK_LAUNCH();
-  hipLaunchKernelGGL(focal_finish_k, dim3(1), dim3(kT), 0, st, (const float*)ws, grid, (double)P, loss);
-  TSG_CHECK_LAUNCH();
-  return 0;
+  return with_elem(dtype, [&](auto t) { return with_label(ltype, [&](auto lt) {
+    typedef typename decltype(t)::type T;
+    hipLaunchKernelGGL((focal_fwd_k<T, lt()>), dim3(grid), dim3(kT), 0, st, (const T*)pred, target, P, ig, gamma, alpha, (float*)ws);
+    TSG_CHECK_LAUNCH();
+    hipLaunchKernelGGL(focal_finish_k, dim3(1), dim3(kT), 0, st, (const float*)ws, grid, (double)P, loss);
+    TSG_CHECK_LAUNCH();
+    return 0;
+  }); });
 }
 
 int tsg_focal_bwd(const void* pred, int dtype, const void* target, int ltype, int64_t P,
@@ -118,14 +116,13 @@ int tsg_focal_bwd(const void* pred, int dtype, const void* target, int ltype, in
   hipStream_t st = (hipStream_t)stream;
   const int grid = fgrid(P) * 4;
   const float ig = (float)ignore_label;
-#define GO(T, LT) hipLaunchKernelGGL((focal_bwd_k<T, LT>), dim3(grid), dim3(kT), 0, st, (const T*)pred, \
-                                     target, P, ig, gamma, alpha, gscale, (T*)dpred)
-  if (dtype == TSG_F32) { if (ltype == TSG_I64) GO(float, TSG_I64); else if (ltype == TSG_U8) GO(float, TSG_U8); else return TSG_E_DTYPE; }
-  else if (dtype == TSG_BF16) { if (ltype == TSG_I64) GO(bf16_t, TSG_I64); else if (ltype == TSG_U8) GO(bf16_t, TSG_U8); else return TSG_E_DTYPE; }
-  else return TSG_E_DTYPE;
-#undef GO
-  TSG_CHECK_LAUNCH();
-  return 0;
+  return with_elem(dtype, [&](auto t) { return with_label(ltype, [&](auto lt) {
+    typedef typename decltype(t)::type T;
+    hipLaunchKernelGGL((focal_bwd_k<T, lt()>), dim3(grid), dim3(kT), 0, st, (const T*)pred, target, P, ig, gamma, alpha, gscale,
+                       (T*)dpred);
+    TSG_CHECK_LAUNCH();
+    return 0;
+  }); });
 }
 
 }  // extern "C"

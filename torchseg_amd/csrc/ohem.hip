@@ -22,7 +22,7 @@
 //
 // HBM-bound: algorithmic bytes per pixel = C*s (fwd) + 2*C*s (bwd) + ~33 B side
 // arrays (labels i64 x2, nll w+r x2, lse w+r).
-#include "tsg_common.h"
+#include "tsg_dispatch.h"
 #include "tsg_resample.h"
 #include <math.h>
 #include <string.h>
@@ -1673,26 +1673,19 @@ int tsg_ohem_fwd(const void* logits, int dtype, const void* labels, int ltype, i
   OhemWs w = carve(ws, pl);
   TSG_HIP(hipMemsetAsync(ws, 0, w.zero_bytes, st));
   const int64_t tb = thresh_tb(thresh);
-  const int native = dtype == TSG_BF16 ? 8 : 4;
+  const int native = native_vec(dtype);
   const bool vec = (HW % native == 0) && aligned16(logits) && aligned16(nll) && aligned16(lse);
   const int bins0 = pl.levels > 0 ? pl.bins[0] : 0;
   static const size_t pa_throttle = [] { const char* e = getenv("TSG_OHEM_FWD_LDS"); return e ? (size_t)atol(e) : (size_t)0; }();
   size_t sh = (size_t)(bins0 > 0 ? bins0 : 1) * sizeof(uint32_t);
   if (sh < pa_throttle) sh = pa_throttle;
-#define PA(T, VV, LTT)                                                                         \
-  hipLaunchKernelGGL((ohem_pass_a<T, VV, LTT>), dim3(pl.grid), dim3(kT), sh, st, (const T*)logits, \
-                     labels, pl.P, C, HW, ignore_label, thresh, tb, pl.shift[0], bins0, weight, \
-                     nll, lse, w.hist[0], w.part)
-  if (dtype == TSG_F32) {
-    if (vec) { if (ltype == TSG_I64) PA(float, 4, TSG_I64); else PA(float, 4, TSG_U8); }
-    else     { if (ltype == TSG_I64) PA(float, 1, TSG_I64); else PA(float, 1, TSG_U8); }
-  } else {
-    if (vec) { if (ltype == TSG_I64) PA(bf16_t, 8, TSG_I64); else PA(bf16_t, 8, TSG_U8); }
-    else     { if (ltype == TSG_I64) PA(bf16_t, 1, TSG_I64); else PA(bf16_t, 1, TSG_U8); }
-  }
-#undef PA
-  TSG_CHECK_LAUNCH();
-  return ohem_select_tail(pl, w, labels, ltype, ignore_label, thresh, min_kept, weight, nll, loss, sel, tb, st);
+  return with_elem_vec(dtype, vec, [&](auto t, auto v) { return with_label(ltype, [&](auto lt) {
+    typedef typename decltype(t)::type T;
+    hipLaunchKernelGGL((ohem_pass_a<T, v(), lt()>), dim3(pl.grid), dim3(kT), sh, st, (const T*)logits, labels, pl.P, C, HW,
+                       ignore_label, thresh, tb, pl.shift[0], bins0, weight, nll, lse, w.hist[0], w.part);
+    TSG_CHECK_LAUNCH();
+    return ohem_select_tail(pl, w, labels, ltype, ignore_label, thresh, min_kept, weight, nll, loss, sel, tb, st);
+  }); });
 }
 
 int tsg_ohem_bwd(const void* logits, int dtype, const void* labels, int ltype, int64_t B, int C,
@@ -1706,7 +1699,7 @@ int tsg_ohem_bwd(const void* logits, int dtype, const void* labels, int ltype, i
   if (B <= 0 || C <= 0 || HW <= 0) return TSG_E_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   const int64_t P = B * HW;
-  const int native = dtype == TSG_BF16 ? 8 : 4;
+  const int native = native_vec(dtype);
   const bool vec = (HW % native == 0) && aligned16(logits) && aligned16(dlogits);
   const int V = vec ? native : 1;
   const int grid = pixel_grid(P / V);
@@ -1714,19 +1707,13 @@ int tsg_ohem_bwd(const void* logits, int dtype, const void* labels, int ltype, i
   // (measured on MI355X, 16x19x1024^2 bf16: 0 B -> 407 us, 40 KB (4 blocks/CU) -> 354 us, 64 KB -> 476 us: with 38
   //  concurrent 2-MB-strided class planes per block, fewer resident blocks thrash DRAM pages / L2 less)
   static const size_t throttle = [] { const char* e = getenv("TSG_OHEM_BWD_LDS"); return e ? (size_t)atol(e) : (size_t)40000; }();
-#define PB(T, VV, LTT)                                                                          \
-  hipLaunchKernelGGL((ohem_bwd_k<T, VV, LTT>), dim3(grid), dim3(kT), throttle, st, (const T*)logits, labels, \
-                     P, C, HW, ignore_label, weight, nll, lse, sel, gscale, (T*)dlogits)
-  if (dtype == TSG_F32) {
-    if (vec) { if (ltype == TSG_I64) PB(float, 4, TSG_I64); else PB(float, 4, TSG_U8); }
-    else     { if (ltype == TSG_I64) PB(float, 1, TSG_I64); else PB(float, 1, TSG_U8); }
-  } else {
-    if (vec) { if (ltype == TSG_I64) PB(bf16_t, 8, TSG_I64); else PB(bf16_t, 8, TSG_U8); }
-    else     { if (ltype == TSG_I64) PB(bf16_t, 1, TSG_I64); else PB(bf16_t, 1, TSG_U8); }
-  }
-#undef PB
-  TSG_CHECK_LAUNCH();
-  return 0;
+  return with_elem_vec(dtype, vec, [&](auto t, auto v) { return with_label(ltype, [&](auto lt) {
+    typedef typename decltype(t)::type T;
+    hipLaunchKernelGGL((ohem_bwd_k<T, v(), lt()>), dim3(grid), dim3(kT), throttle, st, (const T*)logits, labels, P, C, HW,
+                       ignore_label, weight, nll, lse, sel, gscale, (T*)dlogits);
+    TSG_CHECK_LAUNCH();
+    return 0;
+  }); });
 }
 
 // ---- fused upsample + OHEM ------------------------------------------------------
@@ -1768,32 +1755,28 @@ int tsg_ohem_up_fwd(const void* z, int dtype, const void* labels, int ltype, int
     if (B * ((C + kWideBwdCP - 1) / kWideBwdCP) > 65535) return TSG_E_SHAPE;   // the backward's grid.z: refuse here, not after the forward
     const int WCP = upw_fwd_cp(C, IH, IW, OH, OW);
     const size_t wsh = upw_fwd_lds(g, WCP);
-#define PW(T, LTT, CM) hipLaunchKernelGGL((ohem_upw_fwd_k<T, LTT, CM>), dim3(pl.grid), dim3(kT), wsh, st, (const T*)z, labels, B, g, \
-                     ignore_label, thresh, tb, pl.shift[0], bins0, weight, nll, lse, w.hist[0], w.part)
-#define PWC(T, LTT) do { if (WCP == 32) PW(T, LTT, 32); else PW(T, LTT, 16); } while (0)
-    if (dtype == TSG_F32) { if (ltype == TSG_I64) PWC(float, TSG_I64); else PWC(float, TSG_U8); }
-    else { if (ltype == TSG_I64) PWC(bf16_t, TSG_I64); else PWC(bf16_t, TSG_U8); }
-#undef PWC
-#undef PW
-    TSG_CHECK_LAUNCH();
-    return ohem_select_tail(pl, w, labels, ltype, ignore_label, thresh, min_kept, weight, nll, loss, sel, tb, st);
+    return with_elem(dtype, [&](auto t) { return with_label(ltype, [&](auto lt) { return with_int<32, 16>(WCP, [&](auto cp) {
+      typedef typename decltype(t)::type T;
+      hipLaunchKernelGGL((ohem_upw_fwd_k<T, lt(), cp()>), dim3(pl.grid), dim3(kT), wsh, st, (const T*)z, labels, B, g,
+                         ignore_label, thresh, tb, pl.shift[0], bins0, weight, nll, lse, w.hist[0], w.part);
+      TSG_CHECK_LAUNCH();
+      return ohem_select_tail(pl, w, labels, ltype, ignore_label, thresh, min_kept, weight, nll, loss, sel, tb, st);
+    }); }); });
   }
   const int CP = up_class_pad(C);
   const size_t sh = up_fwd_lds(g, CP);
   const bool form2 = up_fwd_form() == 2;
-#define PA(T, LTT, CM)                                                                                \
-  do { if (form2) hipLaunchKernelGGL((ohem_up_fwd2_k<T, LTT, CM>), dim3(pl.grid), dim3(kT), sh, st, (const T*)z, labels, B, g, \
-                     ignore_label, thresh, tb, pl.shift[0], bins0, weight, nll, lse, w.hist[0], w.part); \
-       else hipLaunchKernelGGL((ohem_up_fwd_k<T, LTT, CM>), dim3(pl.grid), dim3(kT), sh, st, (const T*)z, labels, B, g, \
-                     ignore_label, thresh, tb, pl.shift[0], bins0, weight, nll, lse, w.hist[0], w.part); } while (0)
-#define PC(T, LTT) do { switch (CP) { case 8: PA(T, LTT, 8); break; case 16: PA(T, LTT, 16); break; \
-    case 20: PA(T, LTT, 20); break; case 24: PA(T, LTT, 24); break; default: PA(T, LTT, 32); } } while (0)
-  if (dtype == TSG_F32) { if (ltype == TSG_I64) PC(float, TSG_I64); else PC(float, TSG_U8); }
-  else { if (ltype == TSG_I64) PC(bf16_t, TSG_I64); else PC(bf16_t, TSG_U8); }
-#undef PC
-#undef PA
-  TSG_CHECK_LAUNCH();
-  return ohem_select_tail(pl, w, labels, ltype, ignore_label, thresh, min_kept, weight, nll, loss, sel, tb, st);
+  return with_elem(dtype, [&](auto t) { return with_label(ltype, [&](auto lt) { return with_int<8, 16, 20, 24, 32>(CP, [&](auto cp) {
+    typedef typename decltype(t)::type T;
+    if (form2)
+      hipLaunchKernelGGL((ohem_up_fwd2_k<T, lt(), cp()>), dim3(pl.grid), dim3(kT), sh, st, (const T*)z, labels, B, g,
+                         ignore_label, thresh, tb, pl.shift[0], bins0, weight, nll, lse, w.hist[0], w.part);
+    else
+      hipLaunchKernelGGL((ohem_up_fwd_k<T, lt(), cp()>), dim3(pl.grid), dim3(kT), sh, st, (const T*)z, labels, B, g,
+                         ignore_label, thresh, tb, pl.shift[0], bins0, weight, nll, lse, w.hist[0], w.part);
+    TSG_CHECK_LAUNCH();
+    return ohem_select_tail(pl, w, labels, ltype, ignore_label, thresh, min_kept, weight, nll, loss, sel, tb, st);
+  }); }); });
 }
 
 int tsg_ohem_up_bwd(const void* z, int dtype, const void* labels, int ltype, int64_t B, int C, int IH,
@@ -1809,20 +1792,13 @@ int tsg_ohem_up_bwd(const void* z, int dtype, const void* labels, int ltype, int
   hipStream_t st = (hipStream_t)stream;
   const UpBwdCfg cf = up_bwd_cfg(wide ? B * ((C + kWideBwdCP - 1) / kWideBwdCP) : B, C, IH, IW, OH, OW);
   if (!cf.ok) return TSG_E_SHAPE;
-  if (wide) {
-#define PW(T, LTT) return launch_upw_bwd<T, LTT, kWideBwdCP, 512>(cf, B, z, labels, ignore_label, weight, nll, lse, sel, gscale, dz, st)
-    if (dtype == TSG_F32) { if (ltype == TSG_I64) PW(float, TSG_I64); else PW(float, TSG_U8); }
-    else { if (ltype == TSG_I64) PW(bf16_t, TSG_I64); else PW(bf16_t, TSG_U8); }
-#undef PW
-  }
-#define PB(T, LTT, CM, NM) return launch_up_bwd<T, LTT, CM, NM>(cf, B, z, labels, ignore_label, weight, nll, lse, sel, gscale, dz, st)
-#define PC(T, LTT) do { switch (up_class_pad(C)) { case 8: PB(T, LTT, 8, 1024); case 16: PB(T, LTT, 16, 1024); \
-    case 20: PB(T, LTT, 20, 1024); case 24: PB(T, LTT, 24, 512); default: PB(T, LTT, 32, 512); } } while (0)
-  if (dtype == TSG_F32) { if (ltype == TSG_I64) PC(float, TSG_I64); else PC(float, TSG_U8); }
-  else { if (ltype == TSG_I64) PC(bf16_t, TSG_I64); else PC(bf16_t, TSG_U8); }
-#undef PC
-#undef PB
-  return 0;
+  return with_elem(dtype, [&](auto t) { return with_label(ltype, [&](auto lt) {
+    typedef typename decltype(t)::type T;
+    if (wide) return launch_upw_bwd<T, lt(), kWideBwdCP, 512>(cf, B, z, labels, ignore_label, weight, nll, lse, sel, gscale, dz, st);
+    return with_int<8, 16, 20, 24, 32>(up_class_pad(C), [&](auto cp) {         // NTMAX: 1024 threads up to 20 padded classes
+      return launch_up_bwd<T, lt(), cp(), (cp() <= 20 ? 1024 : 512)>(cf, B, z, labels, ignore_label, weight, nll, lse, sel, gscale, dz, st);
+    });
+  }); });
 }
 
 // ---- standalone exact k-th order statistic -----------------------------------

@@ -7,7 +7,7 @@
 // 16x256x128x128 FFM map, profiles/r01); here it is a streaming column reduce
 // with 16-byte loads and fixed-order partials (deterministic), HBM-bound:
 // algorithmic bytes = E*s forward, E*s backward (broadcast write).
-#include "tsg_common.h"
+#include "tsg_dispatch.h"
 
 namespace tsg {
 constexpr int kT = 256;
@@ -551,44 +551,38 @@ int tsg_gap_fwd(const void* x, void* out, int dtype, int layout, int64_t N, int6
   if (N <= 0 || C <= 0 || HW <= 0) return TSG_E_SHAPE;
   if (ws_bytes < tsg_gap_ws_bytes(layout, N, C, HW)) return TSG_E_WS;
   hipStream_t st = (hipStream_t)stream;
-  const int native = dtype == TSG_BF16 ? 8 : 4;
+  const int native = native_vec(dtype);
   const float inv = 1.f / (float)HW;
   if (layout == TSG_NCHW) {
     const bool vec = HW % native == 0 && aligned16(x);
     if (N * C > 0x7fffffffLL) return TSG_E_SHAPE;
     dim3 grid((unsigned)(N * C));
-    if (dtype == TSG_F32) {
-      if (vec) hipLaunchKernelGGL((gap_plane_nchw<float, 4>), grid, dim3(kT), 0, st, (const float*)x, HW, inv, (float*)out);
-      else hipLaunchKernelGGL((gap_plane_nchw<float, 1>), grid, dim3(kT), 0, st, (const float*)x, HW, inv, (float*)out);
-    } else {
-      if (vec) hipLaunchKernelGGL((gap_plane_nchw<bf16_t, 8>), grid, dim3(kT), 0, st, (const bf16_t*)x, HW, inv, (bf16_t*)out);
-      else hipLaunchKernelGGL((gap_plane_nchw<bf16_t, 1>), grid, dim3(kT), 0, st, (const bf16_t*)x, HW, inv, (bf16_t*)out);
-    }
-    TSG_CHECK_LAUNCH();
-    return 0;
+    return with_elem_vec(dtype, vec, [&](auto t, auto v) {
+      typedef typename decltype(t)::type T;
+      hipLaunchKernelGGL((gap_plane_nchw<T, v()>), grid, dim3(kT), 0, st, (const T*)x, HW, inv, (T*)out);
+      TSG_CHECK_LAUNCH();
+      return 0;
+    });
   }
   if (layout != TSG_NHWC) return TSG_E_LAYOUT;
   const int V = (C % native == 0 && aligned16(x)) ? native : 1;
   GapGeom g = gap_geom(N, C, HW, V);
   dim3 grid((unsigned)g.S, (unsigned)N);
   const size_t sh = (size_t)g.R * g.gt * V * (dtype == TSG_F32 ? sizeof(double) : sizeof(float));
-#define GO(T, VV) hipLaunchKernelGGL((gap_partial_nhwc<T, VV>), grid, dim3(kT), sh, st, (const T*)x, HW, C, g.gt, \
-                                     g.R, g.rpb, g.S, (float*)ws)
-  if (dtype == TSG_F32) { if (V == 4) GO(float, 4); else GO(float, 1); }
-  else { if (V == 8) GO(bf16_t, 8); else GO(bf16_t, 1); }
-#undef GO
-  TSG_CHECK_LAUNCH();
-  const int64_t NC = N * C;
-  if (dtype == TSG_F32)
-    hipLaunchKernelGGL((gap_finish<float>), dim3(ceil_div_i(NC, kT)), dim3(kT), 0, st, (const float*)ws, g.S, NC, C, inv, (float*)out);
-  else
-    hipLaunchKernelGGL((gap_finish<bf16_t>), dim3(ceil_div_i(NC, kT)), dim3(kT), 0, st, (const float*)ws, g.S, NC, C, inv, (bf16_t*)out);
-  TSG_CHECK_LAUNCH();
-  return 0;
+  return with_elem_vec(dtype, V != 1, [&](auto t, auto v) {
+    typedef typename decltype(t)::type T;
+    hipLaunchKernelGGL((gap_partial_nhwc<T, v()>), grid, dim3(kT), sh, st, (const T*)x, HW, C, g.gt, g.R, g.rpb, g.S,
+                       (float*)ws);
+    TSG_CHECK_LAUNCH();
+    const int64_t NC = N * C;
+    hipLaunchKernelGGL((gap_finish<T>), dim3(ceil_div_i(NC, kT)), dim3(kT), 0, st, (const float*)ws, g.S, NC, C, inv, (T*)out);
+    TSG_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 size_t tsg_adaptive_avgpool_nhwc_ws_bytes(int dtype, int64_t N, int C, int H, int W, int OH, int OW) {
-  const int V = dtype == TSG_BF16 ? 8 : 4;
+  const int V = native_vec(dtype);
   if (N <= 0 || C <= 0 || C % V || H <= 0 || W <= 0 || OH <= 0 || OW <= 0) return 0;
   const ApGeom g = ap_geom(N, C, H, OH, OW, V);
   return (size_t)N * OH * OW * g.RZ * C * sizeof(float);
@@ -598,7 +592,7 @@ int tsg_adaptive_avgpool_nhwc_fwd(const void* x, void* out, int dtype, int64_t N
                                   void* ws, size_t ws_bytes, void* stream) {
   if (!x || !out || !ws) return TSG_E_NULL;
   if (dtype != TSG_F32 && dtype != TSG_BF16) return TSG_E_DTYPE;
-  const int V = dtype == TSG_BF16 ? 8 : 4;
+  const int V = native_vec(dtype);
   if (N <= 0 || C <= 0 || C % V || H <= 0 || W <= 0 || OH <= 0 || OW <= 0 || OH > H || OW > W) return TSG_E_SHAPE;
   if (N * OH * (int64_t)OW > 0x7fffffffLL) return TSG_E_SHAPE;
   if (ws_bytes < tsg_adaptive_avgpool_nhwc_ws_bytes(dtype, N, C, H, W, OH, OW)) return TSG_E_WS;
@@ -607,41 +601,35 @@ int tsg_adaptive_avgpool_nhwc_fwd(const void* x, void* out, int dtype, int64_t N
   const ApGeom g = ap_geom(N, C, H, OH, OW, V);
   const int64_t bins = N * OH * OW;
   const dim3 grid((unsigned)bins, (unsigned)g.RZ, (unsigned)g.ctiles);
-  if (dtype == TSG_F32)
-    hipLaunchKernelGGL((apool_partial_nhwc<float, 4>), grid, dim3(kT), 0, st, (const float*)x, H, W, C, OH, OW, g.gpb, g.RZ,
-                       (float*)ws);
-  else
-    hipLaunchKernelGGL((apool_partial_nhwc<bf16_t, 8>), grid, dim3(kT), 0, st, (const bf16_t*)x, H, W, C, OH, OW, g.gpb, g.RZ,
-                       (float*)ws);
-  TSG_CHECK_LAUNCH();
   const dim3 fgrid((unsigned)ceil_div_i(bins * C, kT));
-  if (dtype == TSG_F32)
-    hipLaunchKernelGGL((apool_finish<float>), fgrid, dim3(kT), 0, st, (const float*)ws, bins, C, g.RZ, H, W, OH, OW, (float*)out);
-  else
-    hipLaunchKernelGGL((apool_finish<bf16_t>), fgrid, dim3(kT), 0, st, (const float*)ws, bins, C, g.RZ, H, W, OH, OW,
-                       (bf16_t*)out);
-  TSG_CHECK_LAUNCH();
-  return 0;
+  return with_elem(dtype, [&](auto t) {
+    typedef typename decltype(t)::type T;
+    hipLaunchKernelGGL((apool_partial_nhwc<T, Vec<T>::N>), grid, dim3(kT), 0, st, (const T*)x, H, W, C, OH, OW, g.gpb, g.RZ,
+                       (float*)ws);
+    TSG_CHECK_LAUNCH();
+    hipLaunchKernelGGL((apool_finish<T>), fgrid, dim3(kT), 0, st, (const float*)ws, bins, C, g.RZ, H, W, OH, OW, (T*)out);
+    TSG_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 int tsg_adaptive_avgpool_nhwc_bwd(const void* dout, void* dx, int dtype, int64_t N, int C, int H, int W, int OH, int OW,
                                   void* stream) {
   if (!dout || !dx) return TSG_E_NULL;
   if (dtype != TSG_F32 && dtype != TSG_BF16) return TSG_E_DTYPE;
-  const int V = dtype == TSG_BF16 ? 8 : 4;
+  const int V = native_vec(dtype);
   if (N <= 0 || C <= 0 || C % V || H <= 0 || W <= 0 || OH <= 0 || OW <= 0 || OH > H || OW > W) return TSG_E_SHAPE;
   if (!aligned16(dout) || !aligned16(dx)) return TSG_E_ALIGN;
   hipStream_t st = (hipStream_t)stream;
   int64_t blocks = (N * H * (int64_t)W * (C / V) + kT - 1) / kT;
   if (blocks > 8192) blocks = 8192;
-  if (dtype == TSG_F32)
-    hipLaunchKernelGGL((apool_bwd_nhwc<float, 4>), dim3((unsigned)blocks), dim3(kT), 0, st, (const float*)dout, N, H, W, C, OH,
-                       OW, (float*)dx);
-  else
-    hipLaunchKernelGGL((apool_bwd_nhwc<bf16_t, 8>), dim3((unsigned)blocks), dim3(kT), 0, st, (const bf16_t*)dout, N, H, W, C,
-                       OH, OW, (bf16_t*)dx);
-  TSG_CHECK_LAUNCH();
-  return 0;
+  return with_elem(dtype, [&](auto t) {
+    typedef typename decltype(t)::type T;
+    hipLaunchKernelGGL((apool_bwd_nhwc<T, Vec<T>::N>), dim3((unsigned)blocks), dim3(kT), 0, st, (const T*)dout, N, H, W, C, OH,
+                       OW, (T*)dx);
+    TSG_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 int tsg_gap_bwd(const void* dout, void* dx, int dtype, int layout, int64_t N, int64_t C, int64_t HW,
@@ -650,32 +638,29 @@ int tsg_gap_bwd(const void* dout, void* dx, int dtype, int layout, int64_t N, in
   if (dtype != TSG_F32 && dtype != TSG_BF16) return TSG_E_DTYPE;
   if (N <= 0 || C <= 0 || HW <= 0) return TSG_E_SHAPE;
   hipStream_t st = (hipStream_t)stream;
-  const int native = dtype == TSG_BF16 ? 8 : 4;
+  const int native = native_vec(dtype);
   const float inv = 1.f / (float)HW;
   if (layout == TSG_NCHW) {
     const bool vec = HW % native == 0 && aligned16(dx);
     dim3 grid((unsigned)(N * C));
-    if (dtype == TSG_F32) {
-      if (vec) hipLaunchKernelGGL((gap_bwd_nchw<float, 4>), grid, dim3(kT), 0, st, (const float*)dout, HW, inv, (float*)dx);
-      else hipLaunchKernelGGL((gap_bwd_nchw<float, 1>), grid, dim3(kT), 0, st, (const float*)dout, HW, inv, (float*)dx);
-    } else {
-      if (vec) hipLaunchKernelGGL((gap_bwd_nchw<bf16_t, 8>), grid, dim3(kT), 0, st, (const bf16_t*)dout, HW, inv, (bf16_t*)dx);
-      else hipLaunchKernelGGL((gap_bwd_nchw<bf16_t, 1>), grid, dim3(kT), 0, st, (const bf16_t*)dout, HW, inv, (bf16_t*)dx);
-    }
-    TSG_CHECK_LAUNCH();
-    return 0;
+    return with_elem_vec(dtype, vec, [&](auto t, auto v) {
+      typedef typename decltype(t)::type T;
+      hipLaunchKernelGGL((gap_bwd_nchw<T, v()>), grid, dim3(kT), 0, st, (const T*)dout, HW, inv, (T*)dx);
+      TSG_CHECK_LAUNCH();
+      return 0;
+    });
   }
   if (layout != TSG_NHWC) return TSG_E_LAYOUT;
   const int V = (C % native == 0 && aligned16(dx) && aligned16(dout)) ? native : 1;
   int64_t gx = (HW * (C / V) + kT - 1) / kT;
   if (gx > 2048) gx = 2048;
   dim3 grid((unsigned)gx, (unsigned)N);
-#define GO(T, VV) hipLaunchKernelGGL((gap_bwd_nhwc<T, VV>), grid, dim3(kT), 0, st, (const T*)dout, HW, C, inv, (T*)dx)
-  if (dtype == TSG_F32) { if (V == 4) GO(float, 4); else GO(float, 1); }
-  else { if (V == 8) GO(bf16_t, 8); else GO(bf16_t, 1); }
-#undef GO
-  TSG_CHECK_LAUNCH();
-  return 0;
+  return with_elem_vec(dtype, V != 1, [&](auto t, auto v) {
+    typedef typename decltype(t)::type T;
+    hipLaunchKernelGGL((gap_bwd_nhwc<T, v()>), grid, dim3(kT), 0, st, (const T*)dout, HW, C, inv, (T*)dx);
+    TSG_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 
@@ -685,16 +670,16 @@ int tsg_chanscale_fwd(const void* x, const void* s, void* y, int dtype, int layo
   if (dtype != TSG_F32 && dtype != TSG_BF16) return TSG_E_DTYPE;
   if (N <= 0 || C <= 0 || HW <= 0) return TSG_E_SHAPE;
   hipStream_t st = (hipStream_t)stream;
-  const int native = dtype == TSG_BF16 ? 8 : 4;
+  const int native = native_vec(dtype);
   if (layout == TSG_NCHW) {
     const bool vec = HW % native == 0 && aligned16(x) && aligned16(y);
     dim3 grid((unsigned)(N * C));
-#define GO(T, VV, I) hipLaunchKernelGGL((cs_fwd_nchw<T, VV, I>), grid, dim3(kT), 0, st, (const T*)x, (const T*)s, (T*)y, HW)
-    if (dtype == TSG_F32) { if (vec) { if (add_identity) GO(float, 4, true); else GO(float, 4, false); } else { if (add_identity) GO(float, 1, true); else GO(float, 1, false); } }
-    else { if (vec) { if (add_identity) GO(bf16_t, 8, true); else GO(bf16_t, 8, false); } else { if (add_identity) GO(bf16_t, 1, true); else GO(bf16_t, 1, false); } }
-#undef GO
-    TSG_CHECK_LAUNCH();
-    return 0;
+    return with_elem_vec(dtype, vec, [&](auto t, auto v) { return with_flag(add_identity, [&](auto id) {
+      typedef typename decltype(t)::type T;
+      hipLaunchKernelGGL((cs_fwd_nchw<T, v(), id()>), grid, dim3(kT), 0, st, (const T*)x, (const T*)s, (T*)y, HW);
+      TSG_CHECK_LAUNCH();
+      return 0;
+    }); });
   }
   if (layout != TSG_NHWC) return TSG_E_LAYOUT;
   const bool vec = C % native == 0 && aligned16(x) && aligned16(y) && aligned16(s);
@@ -702,12 +687,12 @@ int tsg_chanscale_fwd(const void* x, const void* s, void* y, int dtype, int layo
   int64_t gx = (HW * (C / V) + kT - 1) / kT;
   if (gx > 2048) gx = 2048;
   dim3 grid((unsigned)gx, (unsigned)N);
-#define GO(T, VV, I) hipLaunchKernelGGL((cs_fwd_nhwc<T, VV, I>), grid, dim3(kT), 0, st, (const T*)x, (const T*)s, (T*)y, HW, C)
-  if (dtype == TSG_F32) { if (vec) { if (add_identity) GO(float, 4, true); else GO(float, 4, false); } else { if (add_identity) GO(float, 1, true); else GO(float, 1, false); } }
-  else { if (vec) { if (add_identity) GO(bf16_t, 8, true); else GO(bf16_t, 8, false); } else { if (add_identity) GO(bf16_t, 1, true); else GO(bf16_t, 1, false); } }
-#undef GO
-  TSG_CHECK_LAUNCH();
-  return 0;
+  return with_elem_vec(dtype, vec, [&](auto t, auto v) { return with_flag(add_identity, [&](auto id) {
+    typedef typename decltype(t)::type T;
+    hipLaunchKernelGGL((cs_fwd_nhwc<T, v(), id()>), grid, dim3(kT), 0, st, (const T*)x, (const T*)s, (T*)y, HW, C);
+    TSG_CHECK_LAUNCH();
+    return 0;
+  }); });
 }
 
 int tsg_chanscale_bwd(const void* dy, const void* x, const void* s, void* dx, void* ds, int dtype, int layout,
@@ -718,16 +703,17 @@ int tsg_chanscale_bwd(const void* dy, const void* x, const void* s, void* dx, vo
   if (N <= 0 || C <= 0 || HW <= 0) return TSG_E_SHAPE;
   if (ws_bytes < tsg_gap_ws_bytes(layout, N, C, HW)) return TSG_E_WS;
   hipStream_t st = (hipStream_t)stream;
-  const int native = dtype == TSG_BF16 ? 8 : 4;
+  const int native = native_vec(dtype);
   if (layout == TSG_NCHW) {
     const bool vec = HW % native == 0 && aligned16(x) && aligned16(dy) && aligned16(dx);
     dim3 grid((unsigned)(N * C));
-#define GO(T, VV, I) hipLaunchKernelGGL((cs_bwd_nchw<T, VV, I>), grid, dim3(kT), 0, st, (const T*)dy, (const T*)x, (const T*)s, (T*)dx, (T*)ds, HW)
-    if (dtype == TSG_F32) { if (vec) { if (add_identity) GO(float, 4, true); else GO(float, 4, false); } else { if (add_identity) GO(float, 1, true); else GO(float, 1, false); } }
-    else { if (vec) { if (add_identity) GO(bf16_t, 8, true); else GO(bf16_t, 8, false); } else { if (add_identity) GO(bf16_t, 1, true); else GO(bf16_t, 1, false); } }
-#undef GO
-    TSG_CHECK_LAUNCH();
-    return 0;
+    return with_elem_vec(dtype, vec, [&](auto t, auto v) { return with_flag(add_identity, [&](auto id) {
+      typedef typename decltype(t)::type T;
+      hipLaunchKernelGGL((cs_bwd_nchw<T, v(), id()>), grid, dim3(kT), 0, st, (const T*)dy, (const T*)x, (const T*)s, (T*)dx,
+                         (T*)ds, HW);
+      TSG_CHECK_LAUNCH();
+      return 0;
+    }); });
   }
   if (layout != TSG_NHWC) return TSG_E_LAYOUT;
   const bool vec = C % native == 0 && aligned16(x) && aligned16(dy) && aligned16(dx) && aligned16(s);
@@ -735,19 +721,16 @@ int tsg_chanscale_bwd(const void* dy, const void* x, const void* s, void* dx, vo
   GapGeom g = gap_geom(N, C, HW, V);
   dim3 grid((unsigned)g.S, (unsigned)N);
   const size_t sh = (size_t)g.R * g.gt * V * sizeof(float);
-#define GO(T, VV, I) hipLaunchKernelGGL((cs_bwd_nhwc<T, VV, I>), grid, dim3(kT), sh, st, (const T*)dy, (const T*)x, (const T*)s, \
-                                        (T*)dx, HW, C, g.gt, g.R, g.rpb, g.S, (float*)ws)
-  if (dtype == TSG_F32) { if (vec) { if (add_identity) GO(float, 4, true); else GO(float, 4, false); } else { if (add_identity) GO(float, 1, true); else GO(float, 1, false); } }
-  else { if (vec) { if (add_identity) GO(bf16_t, 8, true); else GO(bf16_t, 8, false); } else { if (add_identity) GO(bf16_t, 1, true); else GO(bf16_t, 1, false); } }
-#undef GO
-  TSG_CHECK_LAUNCH();
-  const int64_t NC = N * C;
-  if (dtype == TSG_F32)
-    hipLaunchKernelGGL((gap_finish<float>), dim3(ceil_div_i(NC, kT)), dim3(kT), 0, st, (const float*)ws, g.S, NC, C, 1.f, (float*)ds);
-  else
-    hipLaunchKernelGGL((gap_finish<bf16_t>), dim3(ceil_div_i(NC, kT)), dim3(kT), 0, st, (const float*)ws, g.S, NC, C, 1.f, (bf16_t*)ds);
-  TSG_CHECK_LAUNCH();
-  return 0;
+  return with_elem_vec(dtype, vec, [&](auto t, auto v) { return with_flag(add_identity, [&](auto id) {
+    typedef typename decltype(t)::type T;
+    hipLaunchKernelGGL((cs_bwd_nhwc<T, v(), id()>), grid, dim3(kT), sh, st, (const T*)dy, (const T*)x, (const T*)s, (T*)dx,
+                       HW, C, g.gt, g.R, g.rpb, g.S, (float*)ws);
+    TSG_CHECK_LAUNCH();
+    const int64_t NC = N * C;
+    hipLaunchKernelGGL((gap_finish<T>), dim3(ceil_div_i(NC, kT)), dim3(kT), 0, st, (const float*)ws, g.S, NC, C, 1.f, (T*)ds);
+    TSG_CHECK_LAUNCH();
+    return 0;
+  }); });
 }
 
 
@@ -761,7 +744,7 @@ int tsg_chanscale_bwd_ds(const void* dy, const void* x, void* ds, int dtype, int
   if (N <= 0 || C <= 0 || HW <= 0) return TSG_E_SHAPE;
   if (layout != TSG_NHWC) return TSG_E_LAYOUT;
   if (ws_bytes < tsg_gap_ws_bytes(layout, N, C, HW)) return TSG_E_WS;
-  const int V = dtype == TSG_BF16 ? 8 : 4;
+  const int V = native_vec(dtype);
   if (C % V) return TSG_E_SHAPE;
   if (!aligned16(x) || !aligned16(dy)) return TSG_E_ALIGN;
   hipStream_t st = (hipStream_t)stream;
@@ -769,20 +752,16 @@ int tsg_chanscale_bwd_ds(const void* dy, const void* x, void* ds, int dtype, int
   dim3 grid((unsigned)g.S, (unsigned)N);
   const size_t sh = (size_t)g.R * g.gt * V * sizeof(float);
   // (s is only read for dx: any valid pointer — x — stands in; IDENT does not matter)
-  if (dtype == TSG_F32)
-    hipLaunchKernelGGL((cs_bwd_nhwc<float, 4, false, false>), grid, dim3(kT), sh, st, (const float*)dy, (const float*)x,
-                       (const float*)x, (float*)nullptr, HW, C, g.gt, g.R, g.rpb, g.S, (float*)ws);
-  else
-    hipLaunchKernelGGL((cs_bwd_nhwc<bf16_t, 8, false, false>), grid, dim3(kT), sh, st, (const bf16_t*)dy, (const bf16_t*)x,
-                       (const bf16_t*)x, (bf16_t*)nullptr, HW, C, g.gt, g.R, g.rpb, g.S, (float*)ws);
-  TSG_CHECK_LAUNCH();
-  const int64_t NC = N * C;
-  if (dtype == TSG_F32)
-    hipLaunchKernelGGL((gap_finish<float>), dim3(ceil_div_i(NC, kT)), dim3(kT), 0, st, (const float*)ws, g.S, NC, C, 1.f, (float*)ds);
-  else
-    hipLaunchKernelGGL((gap_finish<bf16_t>), dim3(ceil_div_i(NC, kT)), dim3(kT), 0, st, (const float*)ws, g.S, NC, C, 1.f, (bf16_t*)ds);
-  TSG_CHECK_LAUNCH();
-  return 0;
+  return with_elem(dtype, [&](auto t) {
+    typedef typename decltype(t)::type T;
+    hipLaunchKernelGGL((cs_bwd_nhwc<T, Vec<T>::N, false, false>), grid, dim3(kT), sh, st, (const T*)dy, (const T*)x,
+                       (const T*)x, (T*)nullptr, HW, C, g.gt, g.R, g.rpb, g.S, (float*)ws);
+    TSG_CHECK_LAUNCH();
+    const int64_t NC = N * C;
+    hipLaunchKernelGGL((gap_finish<T>), dim3(ceil_div_i(NC, kT)), dim3(kT), 0, st, (const float*)ws, g.S, NC, C, 1.f, (T*)ds);
+    TSG_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 int tsg_chanscale_bwd_dx(const void* dy, const void* s, const void* gadd, void* dx, int dtype, int layout, int64_t N, int64_t C,
@@ -791,70 +770,60 @@ int tsg_chanscale_bwd_dx(const void* dy, const void* s, const void* gadd, void* 
   if (dtype != TSG_F32 && dtype != TSG_BF16) return TSG_E_DTYPE;
   if (N <= 0 || C <= 0 || HW <= 0) return TSG_E_SHAPE;
   if (layout != TSG_NHWC) return TSG_E_LAYOUT;
-  const int V = dtype == TSG_BF16 ? 8 : 4;
+  const int V = native_vec(dtype);
   if (C % V) return TSG_E_SHAPE;
   if (!aligned16(dy) || !aligned16(dx) || !aligned16(s) || !aligned16(gadd)) return TSG_E_ALIGN;
   hipStream_t st = (hipStream_t)stream;
   int64_t gx = (HW * (C / V) + kT - 1) / kT;
   if (gx > 2048) gx = 2048;
   dim3 grid((unsigned)gx, (unsigned)N);
-#define GO(T, VV, I) hipLaunchKernelGGL((cs_dx_nhwc<T, VV, I>), grid, dim3(kT), 0, st, (const T*)dy, (const T*)s, (const T*)gadd, (T*)dx, HW, C)
-  if (dtype == TSG_F32) { if (add_identity) GO(float, 4, true); else GO(float, 4, false); }
-  else { if (add_identity) GO(bf16_t, 8, true); else GO(bf16_t, 8, false); }
-#undef GO
-  TSG_CHECK_LAUNCH();
-  return 0;
+  return with_elem(dtype, [&](auto t) { return with_flag(add_identity, [&](auto id) {
+    typedef typename decltype(t)::type T;
+    hipLaunchKernelGGL((cs_dx_nhwc<T, Vec<T>::N, id()>), grid, dim3(kT), 0, st, (const T*)dy, (const T*)s, (const T*)gadd,
+                       (T*)dx, HW, C);
+    TSG_CHECK_LAUNCH();
+    return 0;
+  }); });
 }
 
 int tsg_maxpool_nhwc_fwd(const void* x, void* y, void* argmax_u8, int dtype, int64_t N, int C, int IH, int IW,
                          int OH, int OW, int K, int S, int P, void* stream) {
   if (!x || !y || !argmax_u8) return TSG_E_NULL;
   if (dtype != TSG_F32 && dtype != TSG_BF16) return TSG_E_DTYPE;
-  const int V = dtype == TSG_BF16 ? 8 : 4;
+  const int V = native_vec(dtype);
   if (N <= 0 || C <= 0 || C % V || K <= 0 || K > 15 || S <= 0 || P < 0 || 2 * P > K) return TSG_E_SHAPE;
   if (OH != (IH + 2 * P - K) / S + 1 || OW != (IW + 2 * P - K) / S + 1) return TSG_E_SHAPE;
   if (!aligned16(x) || !aligned16(y)) return TSG_E_ALIGN;
   hipStream_t st = (hipStream_t)stream;
   int64_t g = (N * OH * (int64_t)OW * (C / V) + kT - 1) / kT;
   if (g > 16384) g = 16384;
-  if (dtype == TSG_F32)
-    hipLaunchKernelGGL((maxpool_fwd_nhwc<float, 4>), dim3((unsigned)g), dim3(kT), 0, st, (const float*)x, (float*)y,
+  return with_elem(dtype, [&](auto t) {
+    typedef typename decltype(t)::type T;
+    hipLaunchKernelGGL((maxpool_fwd_nhwc<T, Vec<T>::N>), dim3((unsigned)g), dim3(kT), 0, st, (const T*)x, (T*)y,
                        (uint8_t*)argmax_u8, N, C, IH, IW, OH, OW, K, S, P);
-  else
-    hipLaunchKernelGGL((maxpool_fwd_nhwc<bf16_t, 8>), dim3((unsigned)g), dim3(kT), 0, st, (const bf16_t*)x,
-                       (bf16_t*)y, (uint8_t*)argmax_u8, N, C, IH, IW, OH, OW, K, S, P);
-  TSG_CHECK_LAUNCH();
-  return 0;
+    TSG_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 int tsg_maxpool_nhwc_bwd(const void* dy, const void* argmax_u8, void* dx, int dtype, int64_t N, int C, int IH,
                          int IW, int OH, int OW, int K, int S, int P, void* stream) {
   if (!dy || !dx || !argmax_u8) return TSG_E_NULL;
   if (dtype != TSG_F32 && dtype != TSG_BF16) return TSG_E_DTYPE;
-  const int V = dtype == TSG_BF16 ? 8 : 4;
+  const int V = native_vec(dtype);
   if (N <= 0 || C <= 0 || C % V || K <= 0 || K > 15 || S <= 0 || P < 0) return TSG_E_SHAPE;
   if (!aligned16(dy) || !aligned16(dx)) return TSG_E_ALIGN;
   hipStream_t st = (hipStream_t)stream;
   int64_t g = (N * IH * (int64_t)IW * (C / V) + kT - 1) / kT;
   if (g > 16384) g = 16384;
   const bool fix = K == 3 && S == 2 && P == 1;
-  if (dtype == TSG_F32) {
-    if (fix)
-      hipLaunchKernelGGL((maxpool_bwd_nhwc<float, 4, true>), dim3((unsigned)g), dim3(kT), 0, st, (const float*)dy,
-                         (const uint8_t*)argmax_u8, (float*)dx, N, C, IH, IW, OH, OW, K, S, P);
-    else
-      hipLaunchKernelGGL((maxpool_bwd_nhwc<float, 4, false>), dim3((unsigned)g), dim3(kT), 0, st, (const float*)dy,
-                         (const uint8_t*)argmax_u8, (float*)dx, N, C, IH, IW, OH, OW, K, S, P);
-  } else {
-    if (fix)
-      hipLaunchKernelGGL((maxpool_bwd_nhwc<bf16_t, 8, true>), dim3((unsigned)g), dim3(kT), 0, st, (const bf16_t*)dy,
-                         (const uint8_t*)argmax_u8, (bf16_t*)dx, N, C, IH, IW, OH, OW, K, S, P);
-    else
-      hipLaunchKernelGGL((maxpool_bwd_nhwc<bf16_t, 8, false>), dim3((unsigned)g), dim3(kT), 0, st, (const bf16_t*)dy,
-                         (const uint8_t*)argmax_u8, (bf16_t*)dx, N, C, IH, IW, OH, OW, K, S, P);
-  }
-  TSG_CHECK_LAUNCH();
-  return 0;
+  return with_elem(dtype, [&](auto t) { return with_flag(fix, [&](auto fx) {
+    typedef typename decltype(t)::type T;
+    hipLaunchKernelGGL((maxpool_bwd_nhwc<T, Vec<T>::N, fx()>), dim3((unsigned)g), dim3(kT), 0, st, (const T*)dy,
+                       (const uint8_t*)argmax_u8, (T*)dx, N, C, IH, IW, OH, OW, K, S, P);
+    TSG_CHECK_LAUNCH();
+    return 0;
+  }); });
 }
 
 int tsg_cat2_rows(const void* a, const void* b, void* out, int64_t rows, int64_t row_bytes_a, int64_t row_bytes_b,

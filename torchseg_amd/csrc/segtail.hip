@@ -17,7 +17,7 @@
 // horizontal tap indices and weights of its columns are computed once and shared by every class and row; the vertical
 // ones once per row.  Stores are one 16-byte vector per class plane when the row width allows it (V = 4), else scalar.
 // No atomics: every output element is produced by exactly one thread in a fixed order, so results are bit-reproducible.
-#include "tsg_common.h"
+#include "tsg_dispatch.h"
 #include "tsg_resample.h"
 
 namespace tsg {
@@ -290,25 +290,15 @@ extern "C" int tsg_seg_tail_logprob(const void* z, int dtype, int64_t N, int C, 
   hipStream_t s = (hipStream_t)stream;
   constexpr int RB = 4;
   const int64_t bands = (H + RB - 1) / RB;
-  if (W % 4 == 0) {
-    const int64_t total = N * bands * (W / 4);
-    if (dtype == TSG_BF16)
-      hipLaunchKernelGGL((seg_logprob<bf16_t, 4, RB>), dim3(grid_for(total)), dim3(kT), 0, s, (const bf16_t*)z, out,
-                         (int)N, C, h, w, H, W, sy, sx);
-    else
-      hipLaunchKernelGGL((seg_logprob<float, 4, RB>), dim3(grid_for(total)), dim3(kT), 0, s, (const float*)z, out,
-                         (int)N, C, h, w, H, W, sy, sx);
-  } else {
-    const int64_t total = N * bands * W;
-    if (dtype == TSG_BF16)
-      hipLaunchKernelGGL((seg_logprob<bf16_t, 1, RB>), dim3(grid_for(total)), dim3(kT), 0, s, (const bf16_t*)z, out,
-                         (int)N, C, h, w, H, W, sy, sx);
-    else
-      hipLaunchKernelGGL((seg_logprob<float, 1, RB>), dim3(grid_for(total)), dim3(kT), 0, s, (const float*)z, out,
-                         (int)N, C, h, w, H, W, sy, sx);
-  }
-  TSG_CHECK_LAUNCH();
-  return 0;
+  return with_elem(dtype, [&](auto t) { return with_flag(W % 4 == 0, [&](auto v4) {     // 4 columns per thread, or 1
+    typedef typename decltype(t)::type T;
+    constexpr int V = v4() ? 4 : 1;
+    const int64_t total = N * bands * (W / V);
+    hipLaunchKernelGGL((seg_logprob<T, V, RB>), dim3(grid_for(total)), dim3(kT), 0, s, (const T*)z, out, (int)N, C, h, w, H, W,
+                       sy, sx);
+    TSG_CHECK_LAUNCH();
+    return 0;
+  }); });
 }
 
 extern "C" int tsg_seg_tail_accum_supported(int dtype, int C, int h, int w, int H, int W, int Hd, int Wd) {
@@ -341,13 +331,10 @@ extern "C" int tsg_seg_tail_accum(const void* z, const void* zflip, int dtype, i
   // 16-byte dst access needs every row start and the region's first column on a 4-float boundary
   const bool vec = Wd % 4 == 0 && bx0 % 4 == 0 && ((uintptr_t)dst & 15) == 0;
   const int bh = by1 - by0, bw = bx1 - bx0;
-  if (dtype == TSG_BF16) {
-    if (vec) launch_accum<bf16_t, 4>(z, zflip, geom, dst, (int)N, C, h, w, H, W, Hd, Wd, by0, bx0, bh, bw, accumulate, sy, sx, s);
-    else     launch_accum<bf16_t, 1>(z, zflip, geom, dst, (int)N, C, h, w, H, W, Hd, Wd, by0, bx0, bh, bw, accumulate, sy, sx, s);
-  } else {
-    if (vec) launch_accum<float, 4>(z, zflip, geom, dst, (int)N, C, h, w, H, W, Hd, Wd, by0, bx0, bh, bw, accumulate, sy, sx, s);
-    else     launch_accum<float, 1>(z, zflip, geom, dst, (int)N, C, h, w, H, W, Hd, Wd, by0, bx0, bh, bw, accumulate, sy, sx, s);
-  }
-  TSG_CHECK_LAUNCH();
-  return 0;
+  return with_elem(dtype, [&](auto t) { return with_flag(vec, [&](auto v4) {
+    launch_accum<typename decltype(t)::type, v4() ? 4 : 1>(z, zflip, geom, dst, (int)N, C, h, w, H, W, Hd, Wd, by0, bx0, bh, bw,
+                                                           accumulate, sy, sx, s);
+    TSG_CHECK_LAUNCH();
+    return 0;
+  }); });
 }

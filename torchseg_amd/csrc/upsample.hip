@@ -12,7 +12,7 @@
 // Backward: a GATHER over every source pixel's footprint (no float atomics =>
 // deterministic), the transposed operator evaluated with the forward's exact
 // index/weight arithmetic so that <up(x), g> == <x, up^T(g)> to rounding.
-#include "tsg_common.h"
+#include "tsg_dispatch.h"
 #include "tsg_resample.h"
 
 namespace tsg {
@@ -468,20 +468,17 @@ static int up_fwd_launch(const void* x, const void* add, int add_mode, void* y, 
   if (NC <= 0 || IH <= 0 || IW <= 0 || OH <= 0 || OW <= 0) return TSG_E_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   const float sy = ac_scale(IH, OH), sx = ac_scale(IW, OW);
-  const int native = dtype == TSG_BF16 ? 8 : 4;
+  const int native = native_vec(dtype);
   const bool vec = (OW % native == 0) && aligned16(y) && (add_mode != kAddOut || aligned16(add));
   const int V = vec ? native : 1;
   const int grid = grid_for(NC * ((OH + 15) / 16) * (int64_t)(OW / V));
-#define GO(T, VV, A) hipLaunchKernelGGL((up_fwd<T, VV, A, 16>), dim3(grid), dim3(kT), 0, st, (const T*)x, \
-                                        (const T*)add, (T*)y, NC, IH, IW, OH, OW, sy, sx)
-#define GO3(T, VV) do { if (add_mode == kAddOut) GO(T, VV, kAddOut); else if (add_mode == kAddSrc) GO(T, VV, kAddSrc); \
-                        else GO(T, VV, kAddNone); } while (0)
-  if (dtype == TSG_F32) { if (vec) GO3(float, 4); else GO3(float, 1); }
-  else                  { if (vec) GO3(bf16_t, 8); else GO3(bf16_t, 1); }
-#undef GO3
-#undef GO
-  TSG_CHECK_LAUNCH();
-  return 0;
+  return with_elem_vec(dtype, vec, [&](auto t, auto v) { return with_int<kAddOut, kAddSrc, kAddNone>(add_mode, [&](auto a) {
+    typedef typename decltype(t)::type T;
+    hipLaunchKernelGGL((up_fwd<T, v(), a(), 16>), dim3(grid), dim3(kT), 0, st, (const T*)x, (const T*)add, (T*)y, NC, IH, IW,
+                       OH, OW, sy, sx);
+    TSG_CHECK_LAUNCH();
+    return 0;
+  }); });
 }
 
 int tsg_upsample_bilinear_ac_fwd(const void* x, const void* add, void* y, int dtype, int64_t NC,
@@ -503,8 +500,9 @@ int tsg_upsample_bilinear_ac_bwd(const void* dy, void* dx, int dtype, int64_t NC
   const float sy = ac_scale(IH, OH), sx = ac_scale(IW, OW);
   // widest x-footprint: floor(2/sx) + 4 candidates (see footprint())
   int need = sx > 0.f ? (int)floorf(2.f / sx) + 4 : OW;
+  const int maxf = need <= 9 ? 9 : need <= 21 ? 21 : need <= 37 ? 37 : 0;   // the footprint bound the kernels are built for
   // fast path: up-sampling with a vectorisable row that one block can span
-  const int native = dtype == TSG_BF16 ? 8 : 4;
+  const int native = native_vec(dtype);
   if (need <= 37 && OW % native == 0 && OW / native <= 1024 && OW >= IW && aligned16(dy)) {
     int threads = ((OW / native + 63) / 64) * 64;
     if (threads < 128) threads = 128;
@@ -515,51 +513,42 @@ int tsg_upsample_bilinear_ac_bwd(const void* dy, void* dx, int dtype, int64_t NC
       const int64_t blocks = NC * bands;
       if (blocks <= 0x7fffffffLL) {
         const size_t sh = (size_t)RB * OW * sizeof(float);
-#define GT_(T, VV, F) hipLaunchKernelGGL((up_bwd_tiled<T, VV, F>), dim3((unsigned)blocks), dim3(threads), sh, st, \
-                                         (const T*)dy, (T*)dx, IH, IW, OH, OW, RB, sy, sx)
-        if (dtype == TSG_F32) {
-          if (need <= 9) GT_(float, 4, 9); else if (need <= 21) GT_(float, 4, 21); else GT_(float, 4, 37);
-        } else {
-          if (need <= 9) GT_(bf16_t, 8, 9); else if (need <= 21) GT_(bf16_t, 8, 21); else GT_(bf16_t, 8, 37);
-        }
-#undef GT_
-        TSG_CHECK_LAUNCH();
-        return 0;
+        return with_elem(dtype, [&](auto t) { return with_int<9, 21, 37>(maxf, [&](auto f) {
+          typedef typename decltype(t)::type T;
+          hipLaunchKernelGGL((up_bwd_tiled<T, Vec<T>::N, f()>), dim3((unsigned)blocks), dim3(threads), sh, st, (const T*)dy,
+                             (T*)dx, IH, IW, OH, OW, RB, sy, sx);
+          TSG_CHECK_LAUNCH();
+          return 0;
+        }); });
       }
     }
   }
   const int grid = grid_for(NC * IH * (int64_t)IW);
-#define GO(T, F) hipLaunchKernelGGL((up_bwd<T, F>), dim3(grid), dim3(kT), 0, st, (const T*)dy, (T*)dx, \
-                                    NC, IH, IW, OH, OW, sy, sx)
-  if (dtype == TSG_F32) {
-    if (need <= 9) GO(float, 9); else if (need <= 21) GO(float, 21); else if (need <= 37) GO(float, 37); else GO(float, 0);
-  } else {
-    if (need <= 9) GO(bf16_t, 9); else if (need <= 21) GO(bf16_t, 21); else if (need <= 37) GO(bf16_t, 37); else GO(bf16_t, 0);
-  }
-#undef GO
-  TSG_CHECK_LAUNCH();
-  return 0;
+  return with_elem(dtype, [&](auto t) { return with_int<9, 21, 37, 0>(maxf, [&](auto f) {
+    typedef typename decltype(t)::type T;
+    hipLaunchKernelGGL((up_bwd<T, f()>), dim3(grid), dim3(kT), 0, st, (const T*)dy, (T*)dx, NC, IH, IW, OH, OW, sy, sx);
+    TSG_CHECK_LAUNCH();
+    return 0;
+  }); });
 }
 
 static int up_fwd_nhwc_launch(const void* x, const void* add, int add_mode, void* y, int dtype, int64_t N,
                               int C, int IH, int IW, int OH, int OW, void* stream) {
   if (!x || !y || (add_mode != kAddNone && !add)) return TSG_E_NULL;
   if (dtype != TSG_F32 && dtype != TSG_BF16) return TSG_E_DTYPE;
-  const int V = dtype == TSG_BF16 ? 8 : 4;
+  const int V = native_vec(dtype);
   if (N <= 0 || C <= 0 || C % V || IH <= 0 || IW <= 0 || OH <= 0 || OW <= 0) return TSG_E_SHAPE;
   if (!aligned16(x) || !aligned16(y) || (add && !aligned16(add))) return TSG_E_ALIGN;
   hipStream_t st = (hipStream_t)stream;
   const float sy = ac_scale(IH, OH), sx = ac_scale(IW, OW);
   const int grid = grid_for(N * OH * (int64_t)OW * (C / V));
-#define GO(T, VV, A) hipLaunchKernelGGL((up_fwd_nhwc<T, VV, A>), dim3(grid), dim3(kT), 0, st, (const T*)x, \
-                                        (const T*)add, (T*)y, N, C, IH, IW, OH, OW, sy, sx)
-#define GO3(T, VV) do { if (add_mode == kAddOut) GO(T, VV, kAddOut); else if (add_mode == kAddSrc) GO(T, VV, kAddSrc); \
-                        else GO(T, VV, kAddNone); } while (0)
-  if (dtype == TSG_F32) GO3(float, 4); else GO3(bf16_t, 8);
-#undef GO3
-#undef GO
-  TSG_CHECK_LAUNCH();
-  return 0;
+  return with_elem(dtype, [&](auto t) { return with_int<kAddOut, kAddSrc, kAddNone>(add_mode, [&](auto a) {
+    typedef typename decltype(t)::type T;
+    hipLaunchKernelGGL((up_fwd_nhwc<T, Vec<T>::N, a()>), dim3(grid), dim3(kT), 0, st, (const T*)x, (const T*)add, (T*)y, N, C,
+                       IH, IW, OH, OW, sy, sx);
+    TSG_CHECK_LAUNCH();
+    return 0;
+  }); });
 }
 
 int tsg_upsample_bilinear_ac_nhwc_fwd(const void* x, const void* add, void* y, int dtype, int64_t N,
@@ -576,7 +565,7 @@ int tsg_upsample_bilinear_ac_nhwc_bwd(const void* dy, void* dx, int dtype, int64
                                       int IW, int OH, int OW, void* stream) {
   if (!dy || !dx) return TSG_E_NULL;
   if (dtype != TSG_F32 && dtype != TSG_BF16) return TSG_E_DTYPE;
-  const int V = dtype == TSG_BF16 ? 8 : 4;
+  const int V = native_vec(dtype);
   if (N <= 0 || C <= 0 || C % V || IH <= 0 || IW <= 0 || OH <= 0 || OW <= 0) return TSG_E_SHAPE;
   if (!aligned16(dy) || !aligned16(dx)) return TSG_E_ALIGN;
   hipStream_t st = (hipStream_t)stream;
@@ -592,24 +581,21 @@ int tsg_upsample_bilinear_ac_nhwc_bwd(const void* dy, void* dx, int dtype, int64
     if (gpb < 1) gpb = 1;
     while (gpb > 8 && N * IH * (int64_t)IW * ((G + gpb - 1) / gpb) < 512) gpb >>= 1;
     const dim3 grid2((unsigned)(N * IH * IW), (unsigned)((G + gpb - 1) / gpb));
-    if (dtype == TSG_F32)
-      hipLaunchKernelGGL((up_bwd_nhwc_split<float, 4>), grid2, dim3(256), 0, st, (const float*)dy, (float*)dx, N, C, IH, IW,
-                         OH, OW, sy, sx, gpb);
-    else
-      hipLaunchKernelGGL((up_bwd_nhwc_split<bf16_t, 8>), grid2, dim3(256), 0, st, (const bf16_t*)dy, (bf16_t*)dx, N, C, IH,
-                         IW, OH, OW, sy, sx, gpb);
-    TSG_CHECK_LAUNCH();
-    return 0;
+    return with_elem(dtype, [&](auto t) {
+      typedef typename decltype(t)::type T;
+      hipLaunchKernelGGL((up_bwd_nhwc_split<T, Vec<T>::N>), grid2, dim3(256), 0, st, (const T*)dy, (T*)dx, N, C, IH, IW, OH, OW,
+                         sy, sx, gpb);
+      TSG_CHECK_LAUNCH();
+      return 0;
+    });
   }
   const int grid = grid_for(N * IH * (int64_t)IW * (C / V));
-  if (dtype == TSG_F32)
-    hipLaunchKernelGGL((up_bwd_nhwc<float, 4>), dim3(grid), dim3(kT), 0, st, (const float*)dy, (float*)dx, N, C,
-                       IH, IW, OH, OW, sy, sx);
-  else
-    hipLaunchKernelGGL((up_bwd_nhwc<bf16_t, 8>), dim3(grid), dim3(kT), 0, st, (const bf16_t*)dy, (bf16_t*)dx, N, C,
-                       IH, IW, OH, OW, sy, sx);
-  TSG_CHECK_LAUNCH();
-  return 0;
+  return with_elem(dtype, [&](auto t) {
+    typedef typename decltype(t)::type T;
+    hipLaunchKernelGGL((up_bwd_nhwc<T, Vec<T>::N>), dim3(grid), dim3(kT), 0, st, (const T*)dy, (T*)dx, N, C, IH, IW, OH, OW, sy, sx);
+    TSG_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 int tsg_upsample_nearest_fwd(const void* x, void* y, int elem_bytes, int64_t NC, int IH, int IW,
@@ -640,12 +626,12 @@ int tsg_resize_bilinear_hp(const void* x, float* y, int dtype, int64_t NC, int I
   if (NC <= 0 || IH <= 0 || IW <= 0 || OH <= 0 || OW <= 0) return TSG_E_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   const int grid = grid_for(NC * OH * (int64_t)OW);
-#define GO(T, A) hipLaunchKernelGGL((resize_hp_k<T, A>), dim3(grid), dim3(kT), 0, st, (const T*)x, y, NC, IH, IW, OH, OW)
-  if (dtype == TSG_F32) { if (accumulate) GO(float, true); else GO(float, false); }
-  else { if (accumulate) GO(bf16_t, true); else GO(bf16_t, false); }
-#undef GO
-  TSG_CHECK_LAUNCH();
-  return 0;
+  return with_elem(dtype, [&](auto t) { return with_flag(accumulate != 0, [&](auto acc) {
+    typedef typename decltype(t)::type T;
+    hipLaunchKernelGGL((resize_hp_k<T, acc()>), dim3(grid), dim3(kT), 0, st, (const T*)x, y, NC, IH, IW, OH, OW);
+    TSG_CHECK_LAUNCH();
+    return 0;
+  }); });
 }
 
 }  // extern "C"

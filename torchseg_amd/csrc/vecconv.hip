@@ -10,6 +10,7 @@
 //   data      dx[b][ci] = sum_o  dy[b][o] w[o][ci]                 M = b, N = ci, K = o
 //   weight    dw[o][ci] = sum_b  dy[b][o] x[b][ci]   (fp32 out)    M = o, N = ci, K = b
 #include "tsg_mfma.h"
+#include "tsg_dispatch.h"
 
 namespace tsg {
 
@@ -388,13 +389,12 @@ int tsg_conv1x1_vec_bnact_fwd(const void* x, const float* w, void* out, void* yc
   VcBnArgs bn = {gamma, beta, running_mean, running_var, num_batches_tracked, stats, eps, momentum};
   const dim3 grid((Cout + 31) / 32), blk(64);
   hipStream_t st = (hipStream_t)stream;
-#define L_(M, A) hipLaunchKernelGGL((vec1x1_bnact_fwd_k<M, A>), grid, blk, 0, st, (const bf16_t*)x, w, (bf16_t*)out, (bf16_t*)yc, B, Cin, Cout, bn)
-#define LA_(M) do { if (act == 0) L_(M, 0); else if (act == 1) L_(M, 1); else L_(M, 2); } while (0)
-  if (bnmode == 0) LA_(0); else if (bnmode == 1) LA_(1); else LA_(2);
-#undef LA_
-#undef L_
-  TSG_CHECK_LAUNCH();
-  return 0;
+  return with_int<0, 1, 2>(bnmode, [&](auto m) { return with_int<0, 1, 2>(act, [&](auto a) {
+    hipLaunchKernelGGL((vec1x1_bnact_fwd_k<m(), a()>), grid, blk, 0, st, (const bf16_t*)x, w, (bf16_t*)out, (bf16_t*)yc, B, Cin,
+                       Cout, bn);
+    TSG_CHECK_LAUNCH();
+    return 0;
+  }); });
 }
 
 int tsg_conv1x1_vec_bnact_bwd(const void* dout, const void* out, const void* yc, const float* stats, const void* x,
@@ -409,16 +409,13 @@ int tsg_conv1x1_vec_bnact_bwd(const void* dout, const void* out, const void* yc,
   const size_t sh = (size_t)32 * (size_t)(Cout > 32 ? Cout : 32) * sizeof(uint16_t);
   if (sh > 160 * 1024) return TSG_E_SHAPE;
   hipStream_t st = (hipStream_t)stream;
-#define L_(M, A) do { \
-    if (sh > 64 * 1024) TSG_HIP(hipFuncSetAttribute((const void*)vec1x1_bnact_bwd_k<M, A>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh)); \
-    hipLaunchKernelGGL((vec1x1_bnact_bwd_k<M, A>), dim3(grid), dim3(256), sh, st, (const bf16_t*)dout, (const bf16_t*)out, \
-                       (const bf16_t*)yc, stats, (const bf16_t*)x, w, (bf16_t*)dx, dw, dgamma, dbeta, B, Cin, Cout, ntw); } while (0)
-#define LA_(M) do { if (act == 0) L_(M, 0); else if (act == 1) L_(M, 1); else L_(M, 2); } while (0)
-  if (bnmode == 0) LA_(0); else if (bnmode == 1) LA_(1); else LA_(2);
-#undef LA_
-#undef L_
-  TSG_CHECK_LAUNCH();
-  return 0;
+  return with_int<0, 1, 2>(bnmode, [&](auto m) { return with_int<0, 1, 2>(act, [&](auto a) {
+    if (sh > 64 * 1024) TSG_HIP(hipFuncSetAttribute((const void*)vec1x1_bnact_bwd_k<m(), a()>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+    hipLaunchKernelGGL((vec1x1_bnact_bwd_k<m(), a()>), dim3(grid), dim3(256), sh, st, (const bf16_t*)dout, (const bf16_t*)out,
+                       (const bf16_t*)yc, stats, (const bf16_t*)x, w, (bf16_t*)dx, dw, dgamma, dbeta, B, Cin, Cout, ntw);
+    TSG_CHECK_LAUNCH();
+    return 0;
+  }); });
 }
 
 }  // extern "C"
