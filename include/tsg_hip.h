@@ -545,7 +545,7 @@ int tsg_ohem_up_bwd(const void* z, int dtype, const void* labels, int ltype,
 
 /* The same two entry points for 33 <= C <= 256 classes (ADE20K: 150): tsg_ohem_up_wide_supported() != 0 when
  * tsg_ohem_up_fwd / _bwd take the shape on the class-chunked kernels (ohem_upw_fwd_k: online softmax state per output
- * row carried over chunks of <= 32 classes; ohem_upw_bwd_k: one block per class chunk) under the geometry limits of
+ * row carried over chunks of <= 32 classes; ohem_up_bwd_k<.., WIDE>: one block per class chunk) under the geometry limits of
  * the narrow path.  tsg_ohem_up_supported() keeps answering 0 for C > 32, so a caller opts in to the wide kernels by
  * asking this function.  Same outputs, same selection tail, same determinism. */
 int tsg_ohem_up_wide_supported(int C, int IH, int IW, int OH, int OW);

@@ -1,4 +1,4 @@
-"""The fused upsample + cross-entropy head for 33..256 classes (ohem_upw_fwd_k / ohem_upw_bwd_k behind
+"""The fused upsample + cross-entropy head for 33..256 classes (ohem_upw_fwd_k / ohem_up_bwd_k<.., WIDE> behind
 TSG_FUSE_HEAD_WIDE; ADE20K: 150 classes).  Inputs from the generator of tests/test_fused_head_gpu.py, the oracle is
 oracle.ohem_ref.ohem_cross_entropy on the CPU F.interpolate of the same z, the bounds are the ones that file uses for this
 arithmetic in fp32: loss 1e-4 * max(1, |ref|), max |dz - ref| <= 2e-4 * max |ref grad|, branch and valid count exact.

@@ -1,5 +1,5 @@
 """GPU microbench of the fused upsample + cross-entropy head for 33..256 classes (tsg_ohem_up_fwd / _bwd on
-ohem_upw_fwd_k / ohem_upw_bwd_k, csrc/ohem.hip; TSG_FUSE_HEAD_WIDE) against the materialised chain it replaces on the same
+ohem_upw_fwd_k / ohem_up_bwd_k<.., WIDE>, csrc/ohem.hip; TSG_FUSE_HEAD_WIDE) against the materialised chain it replaces on the same
 operands: upsample_fwd + ohem_fwd + ohem_bwd + upsample_bwd.  Shapes: the ADE20K heads of bench.py, 2 x 150 x 90^2 -> 720^2
 (PSPNet) and 2 x 150 x 60^2 -> 480^2 (PSANet), bf16 logits, uint8 and int64 labels, plain CE (thresh 1, min_kept 0: what
 nn.CrossEntropyLoss of those networks is routed to).

@@ -921,26 +921,34 @@ __global__ __launch_bounds__(kT) void ohem_up_fwd2_k(
 
 struct UpBwdGeom { int C, IH, IW, OH, OW; float sy, sx; int RB, SB, XS; };
 
-template <typename T, int LT, int CP, int NTMAX>
+constexpr int kWideMaxC = 256;
+
+// WIDE (33..256 classes): with lse saved the classes are independent, so a block takes one chunk of CP classes, [c0,
+// c0 + Cc), the chunk being part of blockIdx.z (nchunk per image).  z / dz keep the full C stride.
+template <typename T, int LT, int CP, int NTMAX, bool WIDE>
 __global__ __launch_bounds__(NTMAX) void ohem_up_bwd_k(
-    const T* __restrict__ z, const void* __restrict__ labels, UpBwdGeom g, int64_t ignore_label,
+    const T* __restrict__ z, const void* __restrict__ labels, UpBwdGeom g, int nchunk, int64_t ignore_label,
     const float* __restrict__ weight, const float* __restrict__ nll, const float* __restrict__ lse,
     const int32_t* __restrict__ sel, const float* __restrict__ gscale, T* __restrict__ dz) {
   constexpr int VP = CP + 1;                          // odd row stride: column-major writes and class-major reads both spread over the banks
+  constexpr int OHR = WIDE ? CP + 1 : CP;             // one-hot rows; WIDE: row CP (target outside the chunk) is zero
+  constexpr int WT = WIDE ? kWideMaxC : CP;           // weight table entries: every class a label can name
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int NT = blockDim.x, tid = threadIdx.x;
   const int C = g.C, IH = g.IH, IW = g.IW, OH = g.OH, OW = g.OW, XS = g.XS;
-  float* oh = smem;                                   // [CP][CP] one-hot rows (16-byte aligned rows: CP % 4 == 0)
-  float* Zr = oh + CP * CP;                           // [2][CP][XS] the two live source rows * log2(e)
+  float* oh = smem;                                   // [OHR][CP] one-hot rows (16-byte aligned rows: CP % 4 == 0)
+  float* Zr = oh + OHR * CP;                          // [2][CP][XS] the two live source rows * log2(e)
   float* lxs = Zr + 2 * CP * XS;                      // [NT] lambda_x of every column of the block
   float* Vs = lxs + NT;                               // [NT][VP] a completed source row, before the horizontal taps
   int* xst = reinterpret_cast<int*>(Vs + NT * VP);    // [XS + 2] first column whose x0 is xs_lo + j
-  float* wtab = reinterpret_cast<float*>(xst + XS + 2);   // [CP] gs * class weight: read per pixel from LDS, so that the row
+  float* wtab = reinterpret_cast<float*>(xst + XS + 2);   // [WT] class weight: read per pixel from LDS, so that the row
   //                                                         loop holds no global load whose wait would also wait for the
   //                                                         prefetched next row (round 5: SQ_WAIT_ANY 0.54 was this)
   const int s0 = blockIdx.x * g.SB, s1 = s0 + g.SB < IW ? s0 + g.SB : IW;
   const int r0 = blockIdx.y * g.RB, r1 = r0 + g.RB < IH ? r0 + g.RB : IH;
-  const int64_t b = blockIdx.z;
+  const int64_t b = WIDE ? blockIdx.z / nchunk : blockIdx.z;
+  const int c0 = WIDE ? (int)(blockIdx.z % nchunk) * CP : 0;          // this block's classes: [c0, c0 + Cc)
+  const int Cc = WIDE ? (C - c0 < CP ? C - c0 : CP) : C;
   int xlo, xhi, tmp;
   footprint(g.sx, s0, OW, xlo, tmp);
   footprint(g.sx, s1 - 1, OW, tmp, xhi);
@@ -952,9 +960,10 @@ __global__ __launch_bounds__(NTMAX) void ohem_up_bwd_k(
   src_index0(g.sx, xlo, IW, xs_lo, tmp, tf);
   const int xl0 = x0 - xs_lo, xl1 = x1 - xs_lo;
   lxs[tid] = live ? lx : 0.f;
-  for (int i = tid; i < CP * CP; i += NT) oh[i] = (i / CP == i % CP) ? 1.f : 0.f;
+  for (int i = tid; i < OHR * CP; i += NT) oh[i] = (i / CP == i % CP) ? 1.f : 0.f;
   for (int j = tid; j < XS + 2; j += NT) xst[j] = nact;
-  if (tid < CP) wtab[tid] = (weight && tid < C) ? weight[tid] : 1.f;
+  if constexpr (WIDE) { for (int i = tid; i < WT; i += NT) wtab[i] = (weight && i < C) ? weight[i] : 1.f; }
+  else if (tid < WT) wtab[tid] = (weight && tid < C) ? weight[tid] : 1.f;
   __syncthreads();
   if (live) {
     int p0 = -1, p1; float pf;
@@ -965,7 +974,7 @@ __global__ __launch_bounds__(NTMAX) void ohem_up_bwd_k(
   const int branch = sel[3];
   const float gs = gscale[0] / reinterpret_cast<const float*>(sel)[4];
   const int64_t plane = (int64_t)IH * IW;
-  const T* zb = z + b * C * plane;
+  const T* zb = z + (b * C + c0) * plane;
   // output rows whose y0 lies in [r0-1, r1-1]
   int oy_lo = 0, oy_hi = OH - 1;
   if (g.sy > 0.f) {
@@ -993,8 +1002,8 @@ __global__ __launch_bounds__(NTMAX) void ohem_up_bwd_k(
     }
     __syncthreads();
     const int nS = s1 - s0;
-    for (int idx = tid; idx < C * nS; idx += NT) {
-      const int c = idx % C, s = s0 + idx / C, j = s - xs_lo;
+    for (int idx = tid; idx < Cc * nS; idx += NT) {
+      const int c = idx % Cc, s = s0 + idx / Cc, j = s - xs_lo;
       float sum = 0.f;
       const int xa = xst[j], xb = xst[j + 1];
       for (int x = xa; x < xb; ++x) sum = __builtin_fmaf(1.f - lxs[x], Vs[x * VP + c], sum);
@@ -1002,14 +1011,14 @@ __global__ __launch_bounds__(NTMAX) void ohem_up_bwd_k(
         const int xp = xst[j - 1];
         for (int x = xp; x < xa; ++x) sum = __builtin_fmaf(lxs[x], Vs[x * VP + c], sum);
       }
-      st1<T>(dz + ((b * C + c) * IH + row) * (int64_t)IW + s, sum);
+      st1<T>(dz + ((b * C + c0 + c) * IH + row) * (int64_t)IW + s, sum);
     }
   };
   auto stage = [&](int slot, int y) {
     for (int i = tid; i < CP * XS; i += NT) {
       const int c = i / XS, xx = i % XS;
       const int xg = xs_lo + xx < IW ? xs_lo + xx : IW - 1;
-      Zr[slot * CP * XS + i] = c < C ? ld1<T>(zb + c * plane + (int64_t)y * IW + xg) * kLog2e : kNegBig;
+      Zr[slot * CP * XS + i] = c < Cc ? ld1<T>(zb + c * plane + (int64_t)y * IW + xg) * kLog2e : kNegBig;
     }
   };
   struct Side { typename Lab<LT>::raw_t lab; float nl, ls; };
@@ -1069,7 +1078,8 @@ __global__ __launch_bounds__(NTMAX) void ohem_up_bwd_k(
     if (__builtin_amdgcn_ballot_w64(coef != 0.f) == 0) continue;      // nothing kept in this wave's 64 columns
     const float l2 = sd.ls * kLog2e;
     const float ca = coef - ly * coef, cb = ly * coef;
-    const float4* ohr = reinterpret_cast<const float4*>(oh + t * CP);
+    const int ohrow = !WIDE ? t : (valid && (unsigned)(t - c0) < (unsigned)CP) ? t - c0 : CP;   // CP: the zero row
+    const float4* ohr = reinterpret_cast<const float4*>(oh + ohrow * CP);
     const up_f2 ly2 = {ly, ly}, l22 = {l2, l2}, ca2 = {ca, ca}, cb2 = {cb, cb};
 #pragma unroll
     for (int c4 = 0; c4 < CP / 4; ++c4) {
@@ -1097,11 +1107,8 @@ __global__ __launch_bounds__(NTMAX) void ohem_up_bwd_k(
 //             no underflow case.  The target logit is taken from the window of the chunk that holds the target class,
 //             with the expressions that produce v[t].  The row loop is unrolled (the state is indexed by the row).
 //             Labels sit in LDS as 16-bit values (0xffff = takes no part): class 255 is a class when C = 256.
-//   backward: with lse saved the classes are independent, g_c = coef * (exp2(v_c - lse2) - [c == t]): ohem_up_bwd_k's
-//             structure per class chunk, the chunk being part of blockIdx.z.  z / dz are indexed with the full C stride;
-//             the one-hot row is t - c0 inside the chunk and a row of zeros otherwise.  One owner per dz element.
+//   backward: ohem_up_bwd_k<..., WIDE = true> above, one block per class chunk.  One owner per dz element.
 // =============================================================================
-constexpr int kWideMaxC = 256;
 constexpr int kLabNone = 0xffff;
 
 template <typename T, int LT, int CP>
@@ -1287,168 +1294,6 @@ __global__ __launch_bounds__(kT) void ohem_upw_fwd_k(
   fold_block(acc, lh, bins0, hist0, part);
 }
 
-template <typename T, int LT, int CP, int NTMAX>
-__global__ __launch_bounds__(NTMAX) void ohem_upw_bwd_k(
-    const T* __restrict__ z, const void* __restrict__ labels, UpBwdGeom g, int nchunk, int64_t ignore_label,
-    const float* __restrict__ weight, const float* __restrict__ nll, const float* __restrict__ lse,
-    const int32_t* __restrict__ sel, const float* __restrict__ gscale, T* __restrict__ dz) {
-  constexpr int VP = CP + 1;                          // odd row stride, as in ohem_up_bwd_k
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int NT = blockDim.x, tid = threadIdx.x;
-  const int C = g.C, IH = g.IH, IW = g.IW, OH = g.OH, OW = g.OW, XS = g.XS;
-  float* oh = smem;                                   // [CP + 1][CP] one-hot rows; row CP (target outside the chunk) is zero
-  float* Zr = oh + (CP + 1) * CP;                     // [2][CP][XS] the two live source rows * log2(e)
-  float* lxs = Zr + 2 * CP * XS;                      // [NT] lambda_x of every column of the block
-  float* Vs = lxs + NT;                               // [NT][VP] a completed source row, before the horizontal taps
-  int* xst = reinterpret_cast<int*>(Vs + NT * VP);    // [XS + 2] first column whose x0 is xs_lo + j
-  float* wtab = reinterpret_cast<float*>(xst + XS + 2);   // [kWideMaxC] class weights
-  const int s0 = blockIdx.x * g.SB, s1 = s0 + g.SB < IW ? s0 + g.SB : IW;
-  const int r0 = blockIdx.y * g.RB, r1 = r0 + g.RB < IH ? r0 + g.RB : IH;
-  const int64_t b = blockIdx.z / nchunk;
-  const int c0 = (int)(blockIdx.z % nchunk) * CP;     // this block's classes: [c0, c0 + Cc)
-  const int Cc = C - c0 < CP ? C - c0 : CP;
-  int xlo, xhi, tmp;
-  footprint(g.sx, s0, OW, xlo, tmp);
-  footprint(g.sx, s1 - 1, OW, tmp, xhi);
-  const int nact = xhi - xlo + 1;                     // <= NT (host)
-  const bool live = tid < nact;
-  const int ox = live ? xlo + tid : xhi;
-  int x0, x1, xs_lo; float lx, tf;
-  src_index0(g.sx, ox, IW, x0, x1, lx);
-  src_index0(g.sx, xlo, IW, xs_lo, tmp, tf);
-  const int xl0 = x0 - xs_lo, xl1 = x1 - xs_lo;
-  lxs[tid] = live ? lx : 0.f;
-  for (int i = tid; i < (CP + 1) * CP; i += NT) oh[i] = (i / CP == i % CP) ? 1.f : 0.f;
-  for (int j = tid; j < XS + 2; j += NT) xst[j] = nact;
-  for (int i = tid; i < kWideMaxC; i += NT) wtab[i] = (weight && i < C) ? weight[i] : 1.f;
-  __syncthreads();
-  if (live) {
-    int p0 = -1, p1; float pf;
-    if (tid > 0) src_index0(g.sx, ox - 1, IW, p0, p1, pf);
-    if (p0 != x0) xst[xl0] = tid;                     // OW >= 2 IW: x0 advances by at most 1 per column
-  }
-  const float thr = __uint_as_float((uint32_t)sel[0]);
-  const int branch = sel[3];
-  const float gs = gscale[0] / reinterpret_cast<const float*>(sel)[4];
-  const int64_t plane = (int64_t)IH * IW;
-  const T* zb = z + (b * C + c0) * plane;
-  // output rows whose y0 lies in [r0-1, r1-1]
-  int oy_lo = 0, oy_hi = OH - 1;
-  if (g.sy > 0.f) {
-    const float inv = 1.f / g.sy;
-    const int l = (int)ceilf((float)(r0 - 1) * inv) - 1;
-    const int h = (int)floorf((float)r1 * inv) + 1;
-    oy_lo = l < 0 ? 0 : l;
-    oy_hi = h > OH - 1 ? OH - 1 : h;
-  }
-  up_f2 H0[CP / 2], D[CP / 2], accA[CP / 2], accB[CP / 2];
-#pragma unroll
-  for (int c = 0; c < CP / 2; ++c) { accA[c] = up_f2{0.f, 0.f}; accB[c] = up_f2{0.f, 0.f}; H0[c] = up_f2{0.f, 0.f}; D[c] = up_f2{0.f, 0.f}; }
-  int cur = -2;                                       // source row accA belongs to (accB: cur + 1)
-  int staged0 = -1, staged1 = -1;                     // source rows held by the two ring slots
-
-  auto flush = [&](int row, const up_f2 (&a)[CP / 2]) {   // block-uniform
-    if (row < r0 || row >= r1) return;
-    __syncthreads();                                  // the previous horizontal pass has read Vs
-#pragma unroll
-    for (int c = 0; c < CP / 2; ++c) {
-      Vs[tid * VP + 2 * c] = live ? a[c].x : 0.f;
-      Vs[tid * VP + 2 * c + 1] = live ? a[c].y : 0.f;
-    }
-    __syncthreads();
-    const int nS = s1 - s0;
-    for (int idx = tid; idx < Cc * nS; idx += NT) {
-      const int c = idx % Cc, s = s0 + idx / Cc, j = s - xs_lo;
-      float sum = 0.f;
-      const int xa = xst[j], xb = xst[j + 1];
-      for (int x = xa; x < xb; ++x) sum = __builtin_fmaf(1.f - lxs[x], Vs[x * VP + c], sum);
-      if (j >= 1) {
-        const int xp = xst[j - 1];
-        for (int x = xp; x < xa; ++x) sum = __builtin_fmaf(lxs[x], Vs[x * VP + c], sum);
-      }
-      st1<T>(dz + ((b * C + c0 + c) * IH + row) * (int64_t)IW + s, sum);
-    }
-  };
-  auto stage = [&](int slot, int y) {
-    for (int i = tid; i < CP * XS; i += NT) {
-      const int c = i / XS, xx = i % XS;
-      const int xg = xs_lo + xx < IW ? xs_lo + xx : IW - 1;
-      Zr[slot * CP * XS + i] = c < Cc ? ld1<T>(zb + c * plane + (int64_t)y * IW + xg) * kLog2e : kNegBig;
-    }
-  };
-  struct Side { typename Lab<LT>::raw_t lab; float nl, ls; };
-  auto load_side = [&](int oy) {                      // unconditional, untouched until used: see ohem_up_bwd_k
-    Side sd;
-    const int64_t gp = (b * OH + oy) * (int64_t)OW + ox;
-    sd.lab = Lab<LT>::get_raw(labels, gp);
-    sd.nl = nll[gp];
-    sd.ls = lse[gp];
-    return sd;
-  };
-  Side nxt = load_side(oy_lo);
-  for (int oy = oy_lo; oy <= oy_hi; ++oy) {
-    const Side sd = nxt;
-    if (oy < oy_hi) nxt = load_side(oy + 1);
-    int y0, y1; float ly;
-    src_index0(g.sy, oy, IH, y0, y1, ly);
-    y0 = __builtin_amdgcn_readfirstlane(y0);
-    y1 = __builtin_amdgcn_readfirstlane(y1);
-    if (y0 < r0 - 1 || y0 > r1 - 1) continue;
-    if (y0 != cur) {
-      if (cur >= 0) {
-        flush(cur, accA);
-        if (y0 == cur + 1) {
-#pragma unroll
-          for (int c = 0; c < CP / 2; ++c) { accA[c] = accB[c]; accB[c] = up_f2{0.f, 0.f}; }
-        } else {
-          flush(cur + 1, accB);
-#pragma unroll
-          for (int c = 0; c < CP / 2; ++c) { accA[c] = up_f2{0.f, 0.f}; accB[c] = up_f2{0.f, 0.f}; }
-        }
-      }
-      __syncthreads();                                // everybody has built H0 / D from the rows about to be replaced
-      if (((y0 & 1) ? staged1 : staged0) != y0) { stage(y0 & 1, y0); if (y0 & 1) staged1 = y0; else staged0 = y0; }
-      if (y1 != y0 && ((y1 & 1) ? staged1 : staged0) != y1) { stage(y1 & 1, y1); if (y1 & 1) staged1 = y1; else staged0 = y1; }
-      __syncthreads();
-      const float* za = Zr + (y0 & 1) * CP * XS;
-      const float* zc = Zr + (y1 & 1) * CP * XS;
-#pragma unroll
-      for (int c = 0; c < CP; ++c) {
-        const float a0 = za[c * XS + xl0], a1 = za[c * XS + xl1], b0 = zc[c * XS + xl0], b1 = zc[c * XS + xl1];
-        const float h0 = __builtin_fmaf(lx, a1 - a0, a0), h1 = __builtin_fmaf(lx, b1 - b0, b0);
-        if (c & 1) { H0[c >> 1].y = h0; D[c >> 1].y = h1 - h0; } else { H0[c >> 1].x = h0; D[c >> 1].x = h1 - h0; }
-      }
-      cur = y0;
-    }
-    const int64_t lab = Lab<LT>::widen(sd.lab);
-    const bool valid = live && label_is_class(lab, ignore_label, C);
-    bool kept = valid;
-    if (valid && branch != 2) kept = prob_of_nll(sd.nl) <= thr;
-    const int t = valid ? (int)lab : 0;
-    const float coef = kept ? gs * wtab[t] : 0.f;
-    if (__builtin_amdgcn_ballot_w64(coef != 0.f) == 0) continue;      // nothing kept in this wave's 64 columns
-    const float l2 = sd.ls * kLog2e;
-    const float ca = coef - ly * coef, cb = ly * coef;
-    const int tl = t - c0;
-    const float4* ohr = reinterpret_cast<const float4*>(oh + ((valid && (unsigned)tl < (unsigned)CP) ? tl : CP) * CP);
-    const up_f2 ly2 = {ly, ly}, l22 = {l2, l2}, ca2 = {ca, ca}, cb2 = {cb, cb};
-#pragma unroll
-    for (int c4 = 0; c4 < CP / 4; ++c4) {
-      const float4 o = ohr[c4];
-      const up_f2 ov[2] = {up_f2{o.x, o.y}, up_f2{o.z, o.w}};
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        const int c = c4 * 2 + k;
-        const up_f2 v = __builtin_elementwise_fma(ly2, D[c], H0[c]) - l22;
-        const up_f2 e = up_f2{__builtin_amdgcn_exp2f(v.x), __builtin_amdgcn_exp2f(v.y)} - ov[k];
-        accA[c] = __builtin_elementwise_fma(ca2, e, accA[c]);
-        accB[c] = __builtin_elementwise_fma(cb2, e, accB[c]);
-      }
-    }
-  }
-  if (cur >= 0) { flush(cur, accA); flush(cur + 1, accB); }
-}
-
 static int up_class_pad(int C) { return C <= 8 ? 8 : C <= 16 ? 16 : C <= 20 ? 20 : C <= 24 ? 24 : 32; }
 // 4 register arrays of CP floats per thread.  TSG_HEAD_BWD_NT=512|1024: threads (= output columns) per backward block
 static int up_bwd_ntmax(int CP) {
@@ -1512,11 +1357,15 @@ static UpBwdCfg up_bwd_cfg(int64_t B, int C, int IH, int IW, int OH, int OW) {
   return cf;
 }
 
-static bool up_fused_ok(int C, int IH, int IW, int OH, int OW) {
-  if (C > 32 || C < 1) return false;
-  if (IH < 1 || IW < 1 || OH < 2 * IH || OW < 2 * IW) return false;   // only genuine up-sampling is fused
+// only genuine up-sampling is fused: at least 2x both ways, scales in (0, 0.5]
+static bool up_geom_ok(int IH, int IW, int OH, int OW) {
+  if (IH < 1 || IW < 1 || OH < 2 * IH || OW < 2 * IW) return false;
   const float sx = ac_scale(IW, OW), sy = ac_scale(IH, OH);
-  if (sx <= 0.f || sy <= 0.f || sx > 0.5f || sy > 0.5f) return false;
+  return !(sx <= 0.f || sy <= 0.f || sx > 0.5f || sy > 0.5f);
+}
+
+static bool up_fused_ok(int C, int IH, int IW, int OH, int OW) {
+  if (C > 32 || C < 1 || !up_geom_ok(IH, IW, OH, OW)) return false;
   // the forward's LDS window (z under a 256 x 32 output tile) must leave room for several blocks per CU
   if (up_fwd_lds(up_fwd_geom(C, IH, IW, OH, OW, 2048), up_class_pad(C)) > 64 * 1024) return false;
   return up_bwd_cfg(1, C, IH, IW, OH, OW).ok;
@@ -1535,14 +1384,11 @@ static int upw_fwd_cp(int C, int IH, int IW, int OH, int OW) {
   if (upw_fwd_lds(g, 16) <= 64 * 1024) return 16;
   return 0;
 }
-// ohem_upw_bwd_k's LDS: up_bwd_cfg's figure + the zero one-hot row + a weight table of kWideMaxC instead of CP entries
+// the WIDE backward's LDS: up_bwd_cfg's figure + the zero one-hot row + a weight table of kWideMaxC instead of CP entries
 static size_t upw_bwd_lds(const UpBwdCfg& cf) { return cf.lds + (size_t)kWideMaxC * 4; }
 
 static bool up_wide_ok(int C, int IH, int IW, int OH, int OW) {
-  if (C <= 32 || C > kWideMaxC) return false;
-  if (IH < 1 || IW < 1 || OH < 2 * IH || OW < 2 * IW) return false;   // only genuine up-sampling is fused
-  const float sx = ac_scale(IW, OW), sy = ac_scale(IH, OH);
-  if (sx <= 0.f || sy <= 0.f || sx > 0.5f || sy > 0.5f) return false;
+  if (C <= 32 || C > kWideMaxC || !up_geom_ok(IH, IW, OH, OW)) return false;
   if (upw_fwd_cp(C, IH, IW, OH, OW) == 0) return false;
   return up_bwd_cfg(1, C, IH, IW, OH, OW).ok;
 }
@@ -1602,38 +1448,21 @@ __global__ __launch_bounds__(kT) void target_prob_k(const float* __restrict__ nl
     out[i] = label_is_class(Lab<LT>::get(labels, i), ignore_label, C) ? prob_of_nll(nll[i]) : 1.f;
 }
 
-template <typename T, int LT, int CP, int NTMAX>
+template <typename T, int LT, int CP, int NTMAX, bool WIDE>
 static int launch_up_bwd(const UpBwdCfg& cf, int64_t B, const void* z, const void* labels, int64_t ignore_label,
                          const float* weight, const float* nll, const float* lse, const int32_t* sel,
                          const float* gscale, void* dz, hipStream_t st) {
   static size_t granted = 0;                            // dynamic LDS above 64 KB has to be requested once
-  if (cf.lds > 64 * 1024 && cf.lds > granted) {
-    TSG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ohem_up_bwd_k<T, LT, CP, NTMAX>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)cf.lds));
-    granted = cf.lds;
-  }
-  dim3 grid((unsigned)cf.k, (unsigned)((cf.g.IH + cf.g.RB - 1) / cf.g.RB), (unsigned)B);
-  hipLaunchKernelGGL((ohem_up_bwd_k<T, LT, CP, NTMAX>), grid, dim3(cf.NT), cf.lds, st, (const T*)z, labels, cf.g,
-                     ignore_label, weight, nll, lse, sel, gscale, (T*)dz);
-  TSG_CHECK_LAUNCH();
-  return 0;
-}
-
-template <typename T, int LT, int CP, int NTMAX>
-static int launch_upw_bwd(const UpBwdCfg& cf, int64_t B, const void* z, const void* labels, int64_t ignore_label,
-                          const float* weight, const float* nll, const float* lse, const int32_t* sel,
-                          const float* gscale, void* dz, hipStream_t st) {
-  static size_t granted = 0;                            // dynamic LDS above 64 KB has to be requested once
-  const size_t lds = upw_bwd_lds(cf);
+  const int nchunk = WIDE ? (cf.g.C + CP - 1) / CP : 1;
+  if (WIDE && B * nchunk > 65535) return TSG_E_SHAPE;
+  const size_t lds = WIDE ? upw_bwd_lds(cf) : cf.lds;
   if (lds > 64 * 1024 && lds > granted) {
-    TSG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ohem_upw_bwd_k<T, LT, CP, NTMAX>),
+    TSG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ohem_up_bwd_k<T, LT, CP, NTMAX, WIDE>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     granted = lds;
   }
-  const int nchunk = (cf.g.C + CP - 1) / CP;
-  if (B * nchunk > 65535) return TSG_E_SHAPE;
   dim3 grid((unsigned)cf.k, (unsigned)((cf.g.IH + cf.g.RB - 1) / cf.g.RB), (unsigned)(B * nchunk));
-  hipLaunchKernelGGL((ohem_upw_bwd_k<T, LT, CP, NTMAX>), grid, dim3(cf.NT), lds, st, (const T*)z, labels, cf.g, nchunk,
+  hipLaunchKernelGGL((ohem_up_bwd_k<T, LT, CP, NTMAX, WIDE>), grid, dim3(cf.NT), lds, st, (const T*)z, labels, cf.g, nchunk,
                      ignore_label, weight, nll, lse, sel, gscale, (T*)dz);
   TSG_CHECK_LAUNCH();
   return 0;
@@ -1676,7 +1505,7 @@ int tsg_ohem_fwd(const void* logits, int dtype, const void* labels, int ltype, i
   const int native = native_vec(dtype);
   const bool vec = (HW % native == 0) && aligned16(logits) && aligned16(nll) && aligned16(lse);
   const int bins0 = pl.levels > 0 ? pl.bins[0] : 0;
-  static const size_t pa_throttle = [] { const char* e = getenv("TSG_OHEM_FWD_LDS"); return e ? (size_t)atol(e) : (size_t)0; }();
+  static const size_t pa_throttle = (size_t)tsg_env_int("TSG_OHEM_FWD_LDS", 0);
   size_t sh = (size_t)(bins0 > 0 ? bins0 : 1) * sizeof(uint32_t);
   if (sh < pa_throttle) sh = pa_throttle;
   return with_elem_vec(dtype, vec, [&](auto t, auto v) { return with_label(ltype, [&](auto lt) {
@@ -1706,7 +1535,7 @@ int tsg_ohem_bwd(const void* logits, int dtype, const void* labels, int ltype, i
   // occupancy throttle (tuning knob): unused dynamic LDS caps the resident waves per CU
   // (measured on MI355X, 16x19x1024^2 bf16: 0 B -> 407 us, 40 KB (4 blocks/CU) -> 354 us, 64 KB -> 476 us: with 38
   //  concurrent 2-MB-strided class planes per block, fewer resident blocks thrash DRAM pages / L2 less)
-  static const size_t throttle = [] { const char* e = getenv("TSG_OHEM_BWD_LDS"); return e ? (size_t)atol(e) : (size_t)40000; }();
+  static const size_t throttle = (size_t)tsg_env_int("TSG_OHEM_BWD_LDS", 40000);
   return with_elem_vec(dtype, vec, [&](auto t, auto v) { return with_label(ltype, [&](auto lt) {
     typedef typename decltype(t)::type T;
     hipLaunchKernelGGL((ohem_bwd_k<T, v(), lt()>), dim3(grid), dim3(kT), throttle, st, (const T*)logits, labels, P, C, HW,
@@ -1794,9 +1623,9 @@ int tsg_ohem_up_bwd(const void* z, int dtype, const void* labels, int ltype, int
   if (!cf.ok) return TSG_E_SHAPE;
   return with_elem(dtype, [&](auto t) { return with_label(ltype, [&](auto lt) {
     typedef typename decltype(t)::type T;
-    if (wide) return launch_upw_bwd<T, lt(), kWideBwdCP, 512>(cf, B, z, labels, ignore_label, weight, nll, lse, sel, gscale, dz, st);
+    if (wide) return launch_up_bwd<T, lt(), kWideBwdCP, 512, true>(cf, B, z, labels, ignore_label, weight, nll, lse, sel, gscale, dz, st);
     return with_int<8, 16, 20, 24, 32>(up_class_pad(C), [&](auto cp) {         // NTMAX: 1024 threads up to 20 padded classes
-      return launch_up_bwd<T, lt(), cp(), (cp() <= 20 ? 1024 : 512)>(cf, B, z, labels, ignore_label, weight, nll, lse, sel, gscale, dz, st);
+      return launch_up_bwd<T, lt(), cp(), (cp() <= 20 ? 1024 : 512), false>(cf, B, z, labels, ignore_label, weight, nll, lse, sel, gscale, dz, st);
     });
   }); });
 }
