@@ -134,6 +134,12 @@ class Engine(object):
         logger.info("Load checkpoint from file {}, Time usage:\n\tIO: {}, restore snapshot: {}".format(
             self.continue_state_object, t1 - t0, time.time() - t1))
 
+    def replayed_step(self, model, optimizer, **kw):
+        """The training step captured into a hipGraph and replayed (torchseg_amd/step.py): `loss = step(imgs, gts)`
+        in place of zero_grad / forward / backward / optimizer.step.  It runs eagerly where replay does not apply."""
+        from torchseg_amd.step import ReplayedStep
+        return ReplayedStep(model, optimizer, **kw)
+
     def __enter__(self):
         return self
 
