@@ -474,6 +474,30 @@ int tsg_conv3x3_dil_wrw(const void* x, const void* dy, float* dw, int64_t B, int
                         int dilation, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Weight gradient of the whole-map 1x1 / padding 0 convolutions, stride 1 or 2 (csrc/pwwgrad.hip, plan in
+ * csrc/pw_geom.h): the bottleneck 1x1 layers and `downsample` of furnace/base_model/resnet.py, RefineResidual.conv_1x1 and
+ * FeatureFusion.conv_1x1 of furnace/seg_opr/seg_oprs.py, SpatialPath.conv_1x1 of the bisenet network.py.  Opt-in from
+ * torchseg_amd/pwconv.py (TSG_PW_WGRAD_HIP=1); forward and data gradient of these layers are not part of this family.
+ *     dw[co][ci] = sum_p dy[p][co] * x[row(p)][ci],  p = (b OH + oh) OW + ow,  row(p) = (b H + s oh) W + s ow,
+ *     OH = (H - 1) / s + 1, OW = (W - 1) / s + 1
+ *   x [B,H,W,Cin] and dy [B,OH,OW,Cout]: bf16 channels_last, dense, 16-byte aligned; the stride-2 sub-sampling is part of the
+ *   kernel's addressing (x is the UNgathered input).  dw: fp32 [Cout][Cin], dense, 16-byte aligned.
+ *   tsg_pw_wgrad_supported: 1 exactly for bf16, stride 1 or 2, Cin and Cout multiples of 64 in [64, 2048], B, H, W >= 1 and
+ *     each operand under 2^31 elements (32-bit buffer offsets); every entry point returns TSG_E_DTYPE / TSG_E_SHAPE
+ *     outside that set without launching.
+ *   tsg_pw_wgrad_slices: S, the number of pixel slices, a function of the shape alone (0 = unsupported).
+ *   tsg_pw_wgrad_ws_bytes: S * Cout * Cin * 4 for S > 1, else 0 (also 0 = unsupported).  With S == 1 the kernel writes dw
+ *     itself, ws may be NULL and no fold is launched; a smaller workspace than reported returns TSG_E_WS.
+ *   Rounding: bf16 products accumulate in fp32 (MFMA) inside a slice; the S fp32 partials are added in fp64 in slice order
+ *     and rounded once to fp32.  No atomics, bit-identical from run to run.
+ * ---------------------------------------------------------------------- */
+int tsg_pw_wgrad_supported(int dtype, int Cin, int Cout, int64_t B, int H, int W, int stride);
+int tsg_pw_wgrad_slices(int Cin, int Cout, int64_t B, int H, int W, int stride);
+size_t tsg_pw_wgrad_ws_bytes(int Cin, int Cout, int64_t B, int H, int W, int stride);
+int tsg_pw_wgrad(const void* x, const void* dy, float* dw, int dtype, int64_t B, int H, int W, int Cin, int Cout,
+                 int stride, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * OHEM 2-D cross entropy — replaces ProbOhemCrossEntropy2d.forward
  * (furnace/seg_opr/loss_opr.py:68-98) and the nn.CrossEntropyLoss it ends in.
  * logits are [B, C, HW] (NCHW planar), labels [B*HW].

@@ -79,6 +79,9 @@ upsample overrides.  Controlled by env so train.py needs no edit:
   TSG_PW_CONV=1|0       (default 1 on GPU: the bias-free 1x1 convolutions of whole maps (ResNet shortcuts, SpatialPath.conv_1x1,
                         FeatureFusion.conv_1x1) compute their weight gradient as a chunked batched GEMM folded in a fixed order —
                         the vendor library's split-K atomics were the last run-to-run difference of the step; pwconv.py)
+  TSG_PW_WGRAD_HIP=0|1  (default 0: with 1 that weight gradient comes from tsg_pw_wgrad where it supports the shape — bf16 MFMA over
+                        pixel slices, fp64 fold in slice order, the stride-2 input read in place instead of gathered; every other
+                        case keeps the batched GEMM.  Opt-in: profiles/pwwgrad_bench.txt; pwconv.py, csrc/pwwgrad.hip)
   TSG_FORK_MODULES=a,b  (default none; e.g. "spatial_path": direct sub-modules of an unchanged network.py that run on a side HIP
                         stream and are joined where their output is first used — BiSeNet's detail branch beside its context
                         path.  Box-dependent (+1.4 % / -0.2 %), hence opt-in; our own BiSeNet builder: TSG_FORK_SPATIAL=1; fusion.py)

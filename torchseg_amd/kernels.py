@@ -1140,6 +1140,37 @@ class HipKernels:
                ws.data_ptr(), ws.numel(), L.stream_ptr(x))
         return dw
 
+    # ---- weight gradient of the whole-map 1x1 convolutions (opt-in from pwconv.py; csrc/pwwgrad.hip) ----
+    def pw_wgrad_supported(self, x, dy, stride):
+        """x [B,Cin,H,W], dy [B,Cout,OH,OW] of a 1x1 / padding 0 / stride 1 or 2 convolution: bf16 channels_last, both
+        channel counts multiples of 64 in [64, 2048], each operand under 2^31 elements"""
+        for t in (x, dy):
+            if t.dim() != 4 or t.dtype != torch.bfloat16 or not t.is_contiguous(memory_format=torch.channels_last):
+                return False
+        B, Cin, H, W = x.shape
+        if stride not in (1, 2) or tuple(dy.shape) != (B, dy.shape[1], (H - 1) // stride + 1, (W - 1) // stride + 1):
+            return False
+        return bool(self.lib.tsg_pw_wgrad_supported(L.BF16, Cin, dy.shape[1], B, H, W, int(stride)))
+
+    def pw_wgrad(self, x, dy, stride, out=None):
+        """x [B,Cin,H,W] (the UNgathered input), dy [B,Cout,OH,OW] bf16 channels_last -> dw fp32 [Cout,Cin,1,1] (into `out`
+        when given).  The workspace is a fresh allocation of exactly the reported size (caching allocator: safe under
+        stream capture); none for a single slice."""
+        if not self.pw_wgrad_supported(x, dy, stride):
+            raise L.TsgError("pw_wgrad: unsupported operands %s %s / %s %s, stride %s"
+                             % (tuple(x.shape), x.dtype, tuple(dy.shape), dy.dtype, stride))
+        B, Cin, H, W = x.shape
+        Cout = dy.shape[1]
+        if out is not None and (tuple(out.shape) != (Cout, Cin, 1, 1) or out.dtype != torch.float32
+                                or out.stride(0) != Cin or out.stride(1) != 1 or out.device != x.device):
+            raise ValueError("pw_wgrad: out must be a dense fp32 [Cout, Cin, 1, 1] tensor on the operands' device")
+        dw = out if out is not None else torch.empty((Cout, Cin, 1, 1), dtype=torch.float32, device=x.device)
+        wsb = self.lib.tsg_pw_wgrad_ws_bytes(Cin, Cout, B, H, W, int(stride))
+        ws = torch.empty(int(wsb), dtype=torch.uint8, device=x.device) if wsb else None
+        L.call(self.lib.tsg_pw_wgrad, x.data_ptr(), dy.data_ptr(), dw.data_ptr(), L.BF16, B, H, W, Cin, Cout, int(stride),
+               L.ptr(ws), int(wsb), L.stream_ptr(x))
+        return dw
+
     def conv3x3_s2_dgrad_supported(self, Cin, Cout):
         return bool(self.lib.tsg_conv3x3_s2_dgrad_supported(L.BF16, Cin, Cout))
 

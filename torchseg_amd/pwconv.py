@@ -27,6 +27,10 @@ _DGRAD_MM = os.environ.get("TSG_PW_DGRAD_MM", "1") != "0"
 _SUB_FWD_MM = os.environ.get("TSG_PW_SUB_FWD_MM", "1") != "0"
 # TSG_SEG_DEFER_PW=1|0 (default 1): the weight gradient joins a deferred-launch list when one is open (convwrw._DEFER)
 _DEFER_OK = os.environ.get("TSG_SEG_DEFER_PW", "1") != "0"
+# TSG_PW_WGRAD_HIP=1|0 (default 0): the weight gradient from the library's own kernel (csrc/pwwgrad.hip: bf16 MFMA over pixel
+# slices, fp64 fold in slice order, the stride-2 operand read in place) where it supports the shape; opt-in until its step-level
+# A/B holds (profiles/pwwgrad_bench.txt)
+_HIP_WGRAD = os.environ.get("TSG_PW_WGRAD_HIP", "0") == "1"
 _MIN_CHUNK = 128        # rows of a chunk: below this the batched GEMM's tiles run half empty
 
 
@@ -47,7 +51,13 @@ def _rows(t):
 def pointwise_wgrad(x, dy, stride, out=None):
     """dw [C_out, C_in, 1, 1] fp32 of a 1x1 / padding 0 convolution: x [B, C_in, H, W], dy [B, C_out, OH, OW], both bf16
     channels_last.  Chunked batched GEMM + ordered fold (see the module text).  out: a dense fp32 [C_out, C_in, 1, 1] tensor
-    to write the result into (a deferred launch, convwrw._DEFER: autograd already holds that tensor)."""
+    to write the result into (a deferred launch, convwrw._DEFER: autograd already holds that tensor).
+    With _HIP_WGRAD, HIP operands the library supports go to its kernel instead, x UNgathered."""
+    if _HIP_WGRAD and x.is_cuda and dy.is_cuda:
+        from .kernels import provider
+        kp = provider()
+        if kp.pw_wgrad_supported(x, dy, stride):
+            return kp.pw_wgrad(x, dy, stride, out=out)
     if stride != 1:
         x = x[:, :, ::stride, ::stride].contiguous(memory_format=torch.channels_last)     # the pixels the convolution read
     xr, dr = _rows(x), _rows(dy)
