@@ -917,6 +917,33 @@ int    tsg_dwconv3x3_wgrad(const void* x, const void* dy, float* dw, int dtype, 
                            void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Fused separable unit, inference form (csrc/sepconv.hip) — replaces, per `SeparableConvBnRelu` of
+ * furnace/base_model/xception.py:10-26 in eval mode, the chain tsg_dwconv3x3_fwd -> vendor 1x1 convolution ->
+ * tsg_bn_apply_fwd (with the shortcut addition and ReLU of Block.forward, xception.py:29-63, on a block's last unit) by
+ * one launch:  y = relu?( a * (W_p . dw3x3(x, W_d)) + b (+ residual) ).  The unit has no BatchNorm between its two
+ * convolutions, so the depthwise result never leaves the compute unit.
+ * x channels_last [B, H, W, Cin]; y and residual (may be NULL) channels_last [B, OH, OW, Cout] of x's dtype, OH =
+ * (H - 1) / stride + 1, OW likewise; padding 1, dilation 1, stride 1 or 2; Cin % 8 == 0 in [8, 256], Cout % 16 == 0 in
+ * [16, 256], any H, W >= 1.  x, y, residual and pack 16-byte aligned.
+ * pack: tsg_sepconv_pack_bytes bytes on the device, written by tsg_sepconv_pack (one launch) from wd = the fp32 depthwise
+ * parameter [Cin, 1, 3, 3] (element c*9 + kh*3 + kw), wp = the fp32 point-wise parameter [Cout, Cin, 1, 1] (element
+ * co*Cin + ci) and fwd_pack = what tsg_bn_affine wrote for the unit's BatchNorm (rows 0 and 1: a, b); the layout is
+ * stated in csrc/sep_geom.h.  A pack is specific to (dtype, Cin, Cout).
+ * dtype TSG_BF16: t = dw3x3 formed in fp32 (taps kh-major) and rounded once to bf16, exactly what tsg_dwconv3x3_fwd
+ * stores; W_p rounded to bf16 (nearest even) in the pack; the point-wise sum on v_mfma_f32_32x32x16_bf16, fp32
+ * accumulation; fp32 epilogue fma(a, u, b) (+ float(residual)), ReLU, one rounding to bf16.  TSG_F32 (parity mode):
+ * exact products and fp64 accumulation through the depthwise sum, the point-wise sum and the affine, W_p not rounded,
+ * one rounding to fp32.  No atomics, no sum split across blocks: bit-reproducible.  No host synchronisation and no
+ * allocation: capturable in a graph.  tsg_sepconv_supported is host-only (shape and dtype; alignment is the launcher's
+ * TSG_E_ALIGN). */
+int    tsg_sepconv_supported(int dtype, int Cin, int Cout, int stride, int H, int W);
+size_t tsg_sepconv_pack_bytes(int dtype, int Cin, int Cout);
+int    tsg_sepconv_pack(const float* wd, const float* wp, const float* fwd_pack, int dtype, int Cin, int Cout,
+                        void* pack, void* stream);
+int    tsg_sepconv_fwd(const void* x, const void* pack, const void* residual, void* y, int dtype,
+                       int64_t B, int H, int W, int Cin, int Cout, int stride, int relu, void* stream);
+
+/* ------------------------------------------------------------------------
  * Segmentation head tail (csrc/segtail.hip) — replaces, for an evaluated window, the chain
  * `F.log_softmax(F.interpolate(z, (H, W), mode='bilinear', align_corners=True), dim=1)` of the networks' eval forward,
  * the flip pass, `torch.exp` and the window's `data[...] += score` of furnace/engine/evaluator.py:176-188 / :226-242.

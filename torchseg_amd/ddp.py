@@ -82,6 +82,11 @@ upsample overrides.  Controlled by env so train.py needs no edit:
   TSG_PW_WGRAD_HIP=0|1  (default 0: with 1 that weight gradient comes from tsg_pw_wgrad where it supports the shape — bf16 MFMA over
                         pixel slices, fp64 fold in slice order, the stride-2 input read in place instead of gathered; every other
                         case keeps the batched GEMM.  Opt-in: profiles/pwwgrad_bench.txt; pwconv.py, csrc/pwwgrad.hip)
+  TSG_SEPCONV_FUSED=0|1 (default 0; read by infer.prepare_inference only, never by this wrapper: with 1 the 51 separable units of
+                        Xception39 run as one launch each at inference — depthwise 3x3, point-wise 1x1 on the matrix cores and
+                        the eval-mode BatchNorm (+ shortcut, ReLU) with the depthwise result kept in LDS; training, gradients
+                        enabled, CPU and NCHW inputs keep the stock path.  Opt-in: profiles/x39_infer_bench.txt; sepconv.py,
+                        csrc/sepconv.hip)
   TSG_FORK_MODULES=a,b  (default none; e.g. "spatial_path": direct sub-modules of an unchanged network.py that run on a side HIP
                         stream and are joined where their output is first used — BiSeNet's detail branch beside its context
                         path.  Box-dependent (+1.4 % / -0.2 %), hence opt-in; our own BiSeNet builder: TSG_FORK_SPATIAL=1; fusion.py)

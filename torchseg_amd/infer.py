@@ -10,7 +10,9 @@
     the value is what the network returns;
   - graph=True: the forward is captured once per input shape and dtype (one hipGraph on the capturing stream, no side
     streams: TSG_FORK_MODULES is not applied here) and replayed from a static input buffer.  The returned tensor is that
-    graph's static output: it is overwritten by the next call with the same shape.
+    graph's static output: it is overwritten by the next call with the same shape;
+  - fuse_separable=True (default: TSG_SEPCONV_FUSED, 0): Xception's separable units run as one launch each
+    (torchseg_amd.sepconv.install_fused_separable, after the kernel install; csrc/sepconv.hip).  Opt-in.
 The `+=` / interpolate pre-sum and the ConvBnRelu chain fusions stay gated on autograd as in training (not enabled here).
 """
 import contextlib
@@ -28,7 +30,7 @@ def _compute_dtype(dtype):
 
 
 class InferenceModule(nn.Module):
-    def __init__(self, network, dtype=None, channels_last=None, graph=False):
+    def __init__(self, network, dtype=None, channels_last=None, graph=False, fuse_separable=None):
         super().__init__()
         from . import ddp
         from .syncbn import convert_syncbn_model
@@ -51,6 +53,12 @@ class InferenceModule(nn.Module):
         from .upsample import install_aten_overrides
         install_aten_overrides()
         ddp.install_kernels(self.module, self.compute_dtype)
+        if fuse_separable is None:
+            fuse_separable = ddp._env_flag("TSG_SEPCONV_FUSED", False)
+        self.fused_separable = 0
+        if fuse_separable:
+            from .sepconv import install_fused_separable
+            self.fused_separable = install_fused_separable(self.module)
         self.graph = bool(graph)
         self._graphs = {}
 
@@ -78,6 +86,11 @@ class InferenceModule(nn.Module):
             with torch.no_grad():
                 materialize(self._eager(static_in))          # warm-up: allocations, lazy installs, kernel selection
             torch.cuda.current_stream().synchronize()
+            # the image's bf16 cast belongs to the capture: the stems' cast cache (stemconv._as_bf16_image) still holds the
+            # warm-up's copy of static_in at this version, and a hit would leave the cast out of the graph — every replay
+            # would then read the image of the first call, from memory the graph does not own
+            from . import stemconv
+            stemconv._cast_cache[0] = None
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 static_out = materialize(self._eager(static_in))
@@ -88,11 +101,11 @@ class InferenceModule(nn.Module):
         return static_out
 
 
-def prepare_inference(network, dtype=None, channels_last=None, graph=False):
+def prepare_inference(network, dtype=None, channels_last=None, graph=False, fuse_separable=None):
     """See the module docstring.  `dtype`: torch.bfloat16 or torch.float32 (default: TSG_DTYPE, bf16)."""
     if isinstance(network, InferenceModule):
         return network
-    return InferenceModule(network, dtype=dtype, channels_last=channels_last, graph=graph)
+    return InferenceModule(network, dtype=dtype, channels_last=channels_last, graph=graph, fuse_separable=fuse_separable)
 
 
 def pending_tail(out):

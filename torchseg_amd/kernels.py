@@ -928,6 +928,44 @@ class HipKernels:
                wsb, L.stream_ptr(x))
         return dw
 
+    # ---- fused separable unit, inference form (Xception39; csrc/sepconv.hip) ----
+    def sepconv_supported(self, x, Cout, stride):
+        """x [B,Cin,H,W] channels_last bf16 / fp32, 16-byte aligned; Cout output channels; stride 1 or 2"""
+        if (x.dim() != 4 or x.dtype not in (torch.bfloat16, torch.float32) or x.data_ptr() % 16
+                or not x.is_contiguous(memory_format=torch.channels_last)):
+            return False
+        return bool(self.lib.tsg_sepconv_supported(L.dtype_code(x), x.shape[1], Cout, stride, x.shape[2], x.shape[3]))
+
+    def sepconv_pack(self, wd, wp, fwd_pack, dtype):
+        """wd fp32 [Cin,1,3,3], wp fp32 [Cout,Cin,1,1], fwd_pack fp32 [3,Cout] (tsg_bn_affine) -> the unit's constants
+        for activations of `dtype`, one uint8 device buffer in the layout of csrc/sep_geom.h"""
+        Cout, Cin = wp.shape[0], wp.shape[1]
+        if (wd.dtype != torch.float32 or wp.dtype != torch.float32 or fwd_pack.dtype != torch.float32
+                or tuple(wd.shape) != (Cin, 1, 3, 3) or not _dw_filter_dense(wd) or tuple(wp.shape[2:]) != (1, 1)
+                or wp.stride(0) != Cin or wp.stride(1) != 1 or tuple(fwd_pack.shape) != (3, Cout)):
+            raise L.TsgError("sepconv_pack: dense fp32 filters [Cin,1,3,3] / [Cout,Cin,1,1] and a fwd_pack [3,Cout] needed")
+        _require_contiguous(fwd_pack)
+        dt = L.BF16 if dtype == torch.bfloat16 else L.F32
+        nbytes = self.lib.tsg_sepconv_pack_bytes(dt, Cin, Cout)
+        if nbytes == 0:
+            L.check(-3, "tsg_sepconv_pack_bytes")
+        pack = torch.empty(nbytes, dtype=torch.uint8, device=wp.device)
+        L.call(self.lib.tsg_sepconv_pack, wd.data_ptr(), wp.data_ptr(), fwd_pack.data_ptr(), dt, Cin, Cout, pack.data_ptr(),
+               L.stream_ptr(wp))
+        return pack
+
+    def sepconv_fwd(self, x, pack, Cout, stride, residual, relu):
+        """x [B,Cin,H,W] channels_last -> y [B,Cout,OH,OW] channels_last of x's dtype; residual: None or y's twin"""
+        B, Cin, H, W = x.shape
+        y = torch.empty((B, Cout, (H - 1) // stride + 1, (W - 1) // stride + 1), dtype=x.dtype, device=x.device,
+                        memory_format=torch.channels_last)
+        if residual is not None and (residual.shape != y.shape or residual.dtype != y.dtype
+                                     or not residual.is_contiguous(memory_format=torch.channels_last)):
+            raise L.TsgError("sepconv_fwd: the residual must have the output's shape, dtype and layout")
+        L.call(self.lib.tsg_sepconv_fwd, x.data_ptr(), pack.data_ptr(), L.ptr(residual), y.data_ptr(), L.dtype_code(x), B, H, W,
+               Cin, Cout, stride, int(bool(relu)), L.stream_ptr(x))
+        return y
+
     def sgd_step(self, param, grad, buf, lr, momentum, weight_decay, grad_scale, first):
         L.call(self.lib.tsg_sgd_step, param.data_ptr(), grad.data_ptr(), buf.data_ptr(), param.numel(), float(lr),
                float(momentum), float(weight_decay), float(grad_scale), int(first), L.stream_ptr(param))

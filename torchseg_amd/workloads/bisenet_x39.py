@@ -7,8 +7,10 @@ FeatureFusion and the heads are the R18 builder's.  Module attribute names and c
 hence state dicts are interchangeable and a fixed seed initialises both identically (tests/test_bisenet_x39_cpu.py).
 
 The `.speed` experiment (cityscapes.bisenet.X39.speed) is the same network with head scales 2 / 1 / 1 (labels at 1/8 of
-the crop): the unchanged network.py of that experiment builds on our furnace as it is.  Eager only: none of the R18
-builder's side-stream forks or segmented-graph hooks.
+the crop): the unchanged network.py of that experiment builds on our furnace as it is.  The training step is eager only:
+none of the R18 builder's side-stream forks or segmented-graph hooks.  At inference torchseg_amd.infer.prepare_inference
+captures the forward (graph=True) and, with fuse_separable=True, runs the backbone's 51 separable units as one launch each
+(torchseg_amd/sepconv.py).
 """
 import torch.nn as nn
 import torch.nn.functional as F
