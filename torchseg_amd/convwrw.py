@@ -107,8 +107,9 @@ _WRW_STREAM = _WRW_ENV != "0"
 _WRW_IN_GRAPH = _os.environ.get("TSG_WRW_IN_GRAPH", "0") == "1"
 # A list while a caller wants the 3x3 weight gradients LAUNCHED LATER (bench.SegmentedStep: captured into a graph of their
 # own that replays on another stream beside the rest of the backward pass): wrw_on_side_stream then hands autograd the
-# (still unwritten) result tensor and appends (launch, operands, buffer) to the list.  The caller runs the list and keeps
-# it alive as long as the operands are read.
+# (still unwritten) result tensor and appends (launch, operands, buffer) to the list — for a parameter whose gradient
+# nothing reads before the list runs (may_defer below); any other weight gradient is computed in place and is not listed.
+# The caller runs the list and keeps it alive as long as the operands are read.
 _DEFER = None
 
 
@@ -163,6 +164,53 @@ def _kept_as_gradient(out, param):
     return all(a == b for a, b, n in zip(out.stride(), param.stride(), out.shape) if n != 1)
 
 
+_deferred = {}                         # id(param) -> its entry in _DEFER (None once launched) for THIS backward pass
+_deferred_clear_queued = [False]
+
+
+def _deferred_clear():
+    _deferred_clear_queued[0] = False
+    _deferred.clear()
+
+
+def may_defer(param, buf):
+    """May the weight gradient of `param` be handed to autograd UNWRITTEN (`buf`), its launch only listed in _DEFER?  Only
+    where nothing reads the tensor before the caller runs the list: AccumulateGrad must keep it as it is (a leaf without a
+    gradient, of the buffer's dtype and layout; with a gradient there it would add the unwritten buffer at once), no cast
+    and no hook may touch it, and the parameter must not have another result in this backward pass (the engine would sum
+    the two) — the conditions of the side stream above."""
+    return (param is not None and param.is_leaf and param.grad is None and param.dtype == torch.float32
+            and id(param) not in _wrw_pending and id(param) not in _deferred and not param._backward_hooks
+            and not _foreign_grad_hooks(param) and _kept_as_gradient(buf, param))
+
+
+def note_deferred(param, entry):
+    """List `entry` = (launch, operands, buffer) in _DEFER as the pending weight gradient of `param`."""
+    _DEFER.append(entry)
+    _deferred[id(param)] = entry
+    if not _deferred_clear_queued[0]:
+        _deferred_clear_queued[0] = True
+        from torch.autograd import Variable
+        try:
+            Variable._execution_engine.queue_callback(_deferred_clear)
+        except RuntimeError:                           # not inside a backward pass
+            _deferred_clear()
+
+
+def launch_deferred_of(param):
+    """A second use of a parameter whose first weight gradient of this backward pass was deferred: the engine is about to
+    sum the two, so the listed launch runs now (and leaves the list).  True when `param` had one: the caller then computes
+    in place as well."""
+    if param is None or id(param) not in _deferred:
+        return False
+    entry, _deferred[id(param)] = _deferred[id(param)], None
+    if entry is not None:
+        if _DEFER is not None:
+            _DEFER[:] = [e for e in _DEFER if e is not entry]
+        entry[0]()
+    return True
+
+
 def wrw_on_side_stream(fn, param, *operands, defer_out=None):
     """`fn()` (launches a weight-gradient kernel, returns its result tensor) on the side stream of the operands' device.
     `param`: the parameter the result is the gradient of.  Only a parameter WITHOUT a gradient takes the side stream:
@@ -176,10 +224,13 @@ def wrw_on_side_stream(fn, param, *operands, defer_out=None):
     if _DEFER is not None and defer_out is not None:
         Cout, Cin = defer_out
         buf = torch.empty((Cout, Cin, 3, 3), dtype=torch.float32, device=operands[0].device, memory_format=torch.channels_last)
-        _DEFER.append((lambda: fn(out=buf), operands, buf))
-        # an ALIAS of its own: AccumulateGrad keeps an incoming gradient only when nobody else holds that tensor object, and
-        # clones it otherwise — the copy would be taken here, before the deferred launch has written anything
-        return buf.detach()
+        if may_defer(param, buf):
+            note_deferred(param, (lambda: fn(out=buf), operands, buf))
+            # an ALIAS of its own: AccumulateGrad keeps an incoming gradient only when nobody else holds that tensor object,
+            # and clones it otherwise — the copy would be taken here, before the deferred launch has written anything
+            return buf.detach()
+        if launch_deferred_of(param):                  # (anything else reads the result at once: it is computed in place)
+            return fn()
     if not _WRW_STREAM or not operands[0].is_cuda or param is None or not param.is_leaf or param.grad is not None \
             or param.dtype != torch.float32 or param._backward_hooks or _foreign_grad_hooks(param) \
             or (torch.cuda.is_current_stream_capturing() and not _WRW_IN_GRAPH):

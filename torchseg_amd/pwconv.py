@@ -96,6 +96,7 @@ class _PointwiseFn(torch.autograd.Function):
         ctx.save_for_backward(x, wb)
         ctx.stride = stride
         ctx.wdtype = weight.dtype
+        ctx.wparam = weight                            # (not a graph tensor here: only what may_defer asks of it is looked at)
         return y
 
     @staticmethod
@@ -116,16 +117,19 @@ class _PointwiseFn(torch.autograd.Function):
         dw = None
         if ctx.needs_input_grad[1]:
             from . import convwrw
-            if convwrw._DEFER is not None and _DEFER_OK and ctx.wdtype == torch.float32:
+            buf = None
+            if convwrw._DEFER is not None and _DEFER_OK:
+                buf = torch.empty((dy.shape[1], x.shape[1], 1, 1), dtype=torch.float32, device=dy.device)
+            if buf is not None and convwrw.may_defer(ctx.wparam, buf):
                 # bench.SegmentedStep: listed, launched later from a graph of its own beside the next part of the backward;
                 # autograd gets the still unwritten result (an alias of its own: see convwrw.wrw_on_side_stream)
-                buf = torch.empty((dy.shape[1], x.shape[1], 1, 1), dtype=torch.float32, device=dy.device)
                 def later():                                   # (outside backward: grad mode is on again, x may require grad)
                     with torch.no_grad():
                         pointwise_wgrad(x, dy, st, out=buf)
-                convwrw._DEFER.append((later, (x, dy), buf))
+                convwrw.note_deferred(ctx.wparam, (later, (x, dy), buf))
                 dw = buf.detach()
             else:
+                convwrw.launch_deferred_of(ctx.wparam)
                 dw = pointwise_wgrad(x, dy, st)
                 if dw.dtype != ctx.wdtype:
                     dw = dw.to(ctx.wdtype)
