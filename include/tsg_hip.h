@@ -944,6 +944,35 @@ int    tsg_sepconv_fwd(const void* x, const void* pack, const void* residual, vo
                        int64_t B, int H, int W, int Cin, int Cout, int stride, int relu, void* stream);
 
 /* ------------------------------------------------------------------------
+ * 3x3 convolution + BatchNorm (+ residual) (+ ReLU), inference form (csrc/convbn.hip) — replaces, in eval mode, the chain
+ * tsg_conv3x3_gen_fwd (or tsg_conv3x3_c64_fwd) -> tsg_bn_apply_fwd of ResNet's BasicBlock / Bottleneck.conv2
+ * (furnace/base_model/resnet.py:36-53, :80-101) and of the 3x3 ConvBnRelu layers (seg_oprs.py:24-46) by one launch:
+ *   y = bf16( relu?( fma(ab[0][oc], u, ab[1][oc]) + float(residual) ) ),
+ * u the fp32 MFMA accumulation of the 3x3 / stride 1 / padding 1 / dilation 1 convolution of bf16 operands.  There is ONE
+ * rounding, at the store: the result is not bit-equal to the two-launch chain, which rounds u to bf16 first.
+ * x [B,H,W,Cin], residual (may be NULL) and y [B,H,W,Cout]: bf16 channels_last, dense, 16-byte aligned; y must not alias x
+ * or the residual.  Cin % 16 == 0, Cout % 64 == 0 (the 64 -> 64 layers included); one image of x or y holds less than
+ * 2^31 elements and B * ceil(H / 8) * ceil(W / 32) < 2^31 (csrc/cbn_geom.h states the plan and these limits).
+ * ab: fp32 [2][Cout], 16-byte aligned: rows 0 and 1 of what tsg_bn_affine wrote for the BatchNorm; a convolution bias is
+ *   folded by the caller, ab[1] += ab[0] * bias.
+ * wf: 9 * Cin * Cout bf16 = tsg_conv3x3_gen_prep_filter(w', TSG_F32 or TSG_BF16, wf, Cout, Cin, mode 0, BN 64) of the
+ *   weight [Cout][3][3][Cin] whose OUTPUT CHANNELS WERE PERMUTED inside every group of 64:
+ *     w'[64 t + q] = w[64 t + perm[q]],  perm = tsg_conv3x3_bnact_row_perm (a bijection of [0, 64); the one definition is
+ *   cbn_row_cout of csrc/cbn_geom.h).  With it a lane's 16 MFMA accumulator registers are 16 consecutive output channels
+ *   and the epilogue needs no staging image.  A filter prepared from the unpermuted weight gives permuted channels.
+ * tsg_conv3x3_bnact_supported: 1 exactly for TSG_BF16 and a shape inside the limits above (host-only; pointer alignment
+ *   is the launcher's TSG_E_ALIGN).
+ * tsg_conv3x3_bnact_plan: out5 = {pixel tiles of 8 x 32 per oc tile, persistent blocks per oc tile, oc tiles, grid, bytes of
+ *   LDS per block}; a block walks the tiles slot, slot + out5[1], ...  A function of the shape alone, informational (tests).
+ * No atomics, no sum split across blocks, no device query, no environment switch: bit-identical from launch to launch.
+ * No host synchronisation and no allocation: capturable in a graph. */
+int tsg_conv3x3_bnact_supported(int dtype, int64_t B, int64_t H, int64_t W, int Cin, int Cout);
+int tsg_conv3x3_bnact_row_perm(int* out64);
+int tsg_conv3x3_bnact_plan(int64_t B, int64_t H, int64_t W, int Cin, int Cout, int* out5);
+int tsg_conv3x3_bnact_fwd(const void* x, const void* wf, const float* ab, const void* residual, void* y, int64_t B,
+                          int64_t H, int64_t W, int Cin, int Cout, int relu, void* stream);
+
+/* ------------------------------------------------------------------------
  * Segmentation head tail (csrc/segtail.hip) — replaces, for an evaluated window, the chain
  * `F.log_softmax(F.interpolate(z, (H, W), mode='bilinear', align_corners=True), dim=1)` of the networks' eval forward,
  * the flip pass, `torch.exp` and the window's `data[...] += score` of furnace/engine/evaluator.py:176-188 / :226-242.

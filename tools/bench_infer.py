@@ -19,6 +19,19 @@ separable units (prepare_inference(fuse_separable=), csrc/sepconv.hip) off and o
              of each off arm against itself, (max - min) / median: a difference between off and on below that is noise.
 
     python tools/bench_infer.py --model x39 [--quick] [--reps 3]
+
+--model r18 --convbn: the same arm scheme and protocol for BiSeNet-R18 with the fused 3x3 convolution + BatchNorm layers
+(prepare_inference(fuse_convbn=), csrc/convbn.hip) off and on.  The off arm is the code path without the switch.
+
+    python tools/bench_infer.py --model r18 --convbn [--quick] [--reps 3]
+
+--model r18 --layers: per-layer figures of that kernel, CACHE-WARM MICRO-BENCHMARKS (one layer in a loop on the same
+tensors: its operands stay in L2 / Infinity Cache, which is not where a layer finds them inside a network): the fused call
+against tsg_conv3x3_gen_fwd + tsg_bn_apply_fwd (with the shortcut and ReLU) at the four backbone stage shapes of
+BiSeNet-R18 for a 768 x 1536 image, off / on alternated `--reps` times, every timing a window of >= 0.25 s between two
+device events.
+
+    python tools/bench_infer.py --model r18 --layers [--reps 3]
 """
 import argparse
 import copy
@@ -49,8 +62,8 @@ def x39():
     return BiSeNetX39(19, False, None, None, pretrained_model=None, norm_layer=nn.BatchNorm2d).eval()
 
 
-X39_RES = ((768, 1536), (1024, 2048))
-X39_ARMS = ("stock_fp32", "eager_bf16_off", "eager_bf16_on", "graph_bf16_off", "graph_bf16_on")
+ARM_RES = ((768, 1536), (1024, 2048))
+ARMS = ("stock_fp32", "eager_bf16_off", "eager_bf16_on", "graph_bf16_off", "graph_bf16_on")
 
 
 def event_times(fn, iters, warmup):
@@ -67,24 +80,30 @@ def event_times(fn, iters, warmup):
     return [a.elapsed_time(b) for a, b in pairs]
 
 
-def x39_arm(arm, iters, warmup):
+# model -> (builder, title, prepare_inference's switch, attribute with the installed count, that count, module of fused_calls)
+ARM_MODELS = {"x39": (x39, "BiSeNet-X39", "fuse_separable", "fused_separable", 51, "sepconv"),
+              "r18": (r18, "BiSeNet-R18", "fuse_convbn", "fused_convbn", 20, "convbn")}
+
+
+def arm_times(arm, iters, warmup, model="x39"):
     """one arm in this (child) process -> {"HxW": median ms, ...}"""
+    import importlib
     from torchseg_amd.fusion import materialize
     from torchseg_amd.infer import prepare_inference
-    from torchseg_amd.sepconv import fused_calls
+    build, _, switch, counter, count, where = ARM_MODELS[model]
+    fused_calls = importlib.import_module("torchseg_amd." + where).fused_calls
     dev = torch.device("cuda:0")
-    net = x39().to(dev)
+    net = build().to(dev)
     if arm == "stock_fp32":
         def run(x):
             with torch.no_grad():
                 return net(x)
     else:
-        prep = prepare_inference(net, dtype=torch.bfloat16, graph=arm.startswith("graph"),
-                                 fuse_separable=arm.endswith("_on"))
-        assert prep.fused_separable == (51 if arm.endswith("_on") else 0)
+        prep = prepare_inference(net, dtype=torch.bfloat16, graph=arm.startswith("graph"), **{switch: arm.endswith("_on")})
+        assert getattr(prep, counter) == (count if arm.endswith("_on") else 0)
         run = (lambda x: prep(x)) if prep.graph else (lambda x: materialize(prep(x)))
     out = {}
-    for res in X39_RES:
+    for res in ARM_RES:
         x = torch.randn(1, 3, *res, device=dev)
         out["%dx%d" % res] = float(np.median(event_times(lambda: run(x), iters, warmup)))
     if arm.endswith("_on"):
@@ -92,11 +111,12 @@ def x39_arm(arm, iters, warmup):
     return out
 
 
-def x39_table(iters, warmup, reps):
+def arm_table(iters, warmup, reps, model="x39"):
     import subprocess
+    title = ARM_MODELS[model][1]
 
     def child(arm):
-        cmd = [sys.executable, os.path.abspath(__file__), "--model", "x39", "--arm", arm, "--iters", str(iters),
+        cmd = [sys.executable, os.path.abspath(__file__), "--model", model, "--arm", arm, "--iters", str(iters),
                "--warmup", str(warmup)]
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
         if r.returncode != 0:
@@ -104,20 +124,20 @@ def x39_table(iters, warmup, reps):
         print("%s: %s" % (arm, r.stdout.strip().splitlines()[-1]), file=sys.stderr, flush=True)
         return json.loads(r.stdout.strip().splitlines()[-1])
 
-    runs = {arm: [] for arm in X39_ARMS}
+    runs = {arm: [] for arm in ARMS}
     runs["stock_fp32"].append(child("stock_fp32"))
     for _ in range(reps):                                   # off and on alternate
         for arm in ("graph_bf16_off", "graph_bf16_on", "eager_bf16_off", "eager_bf16_on"):
             runs[arm].append(child(arm))
-    result = {"device": torch.cuda.get_device_name(0), "model": "BiSeNet-X39", "iters": iters, "warmup": warmup,
+    result = {"device": torch.cuda.get_device_name(0), "model": title, "iters": iters, "warmup": warmup,
               "reps": reps, "runs_ms": runs}
-    print("BiSeNet-X39 forward, batch 1, ms per call: median over %d child processes (min-max); %d timed calls per child, "
-          "device events" % (reps, iters))
+    print("%s forward, batch 1, ms per call: median over %d child processes (min-max); %d timed calls per child, "
+          "device events" % (title, reps, iters))
     print("%-16s %-28s %-28s" % ("arm", "1x3x768x1536", "1x3x1024x2048"))
     summary = {}
-    for arm in X39_ARMS:
+    for arm in ARMS:
         cells = []
-        for res in X39_RES:
+        for res in ARM_RES:
             v = [r["%dx%d" % res] for r in runs[arm]]
             med = float(np.median(v))
             summary.setdefault(arm, {})["%dx%d" % res] = dict(median_ms=med, min_ms=min(v), max_ms=max(v),
@@ -125,7 +145,7 @@ def x39_table(iters, warmup, reps):
             cells.append("%.3f (%.3f-%.3f)" % (med, min(v), max(v)))
         print("%-16s %-28s %-28s" % (arm, cells[0], cells[1]))
     for kind in ("graph", "eager"):
-        for res in X39_RES:
+        for res in ARM_RES:
             k = "%dx%d" % res
             off, on = summary[kind + "_bf16_off"][k], summary[kind + "_bf16_on"][k]
             gain = 1.0 - on["median_ms"] / off["median_ms"]
@@ -134,6 +154,83 @@ def x39_table(iters, warmup, reps):
                      "beyond the spread" if abs(gain) > off["spread"] else "WITHIN the spread (no difference shown)"))
     result["summary"] = summary
     print(json.dumps(result))
+
+
+R18_LAYERS = ((192, 384, 64), (96, 192, 128), (48, 96, 256), (24, 48, 512))      # (H, W, C) of layer1-4 at 768 x 1536
+
+
+def window_ms(fn, min_s=0.25):
+    """ms per call of fn over one window of at least `min_s` seconds between two device events"""
+    for _ in range(5):
+        fn()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    n = 20
+    while True:
+        torch.cuda.synchronize()
+        a.record()
+        for _ in range(n):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        ms = a.elapsed_time(b)
+        if ms >= 1e3 * min_s:
+            return ms / n
+        n = int(n * max(2.0, 1.2e3 * min_s / max(ms, 1e-3)))
+
+
+GRAPH_CALLS = 20
+
+
+def graphed(fn):
+    """GRAPH_CALLS calls of fn captured in one graph -> its replay"""
+    fn()
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(GRAPH_CALLS):
+            fn()
+    return g.replay
+
+
+def r18_layers(reps):
+    """the block tail conv3x3 -> BatchNorm -> + shortcut -> ReLU at BiSeNet-R18's four stage shapes: two launches against one"""
+    from torchseg_amd import _lib as L, kernels as K
+    kp = K.provider()
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(0)
+    CL = torch.channels_last
+    rows = []
+    print("CACHE-WARM MICRO-BENCHMARKS: one layer in a loop on the same tensors (%d calls per graph replay), us per call, median "
+          "of %d windows of >= 0.25 s (min-max), unfused / fused alternated" % (GRAPH_CALLS, reps))
+    print("%-22s %-30s %-30s %s" % ("layer (B x H x W x C)", "gen_fwd + bn_apply_fwd", "conv3x3_bnact_fwd", "fused / unfused"))
+    for H, W, Cc in R18_LAYERS:
+        x = torch.randn(1, Cc, H, W, generator=g).to(dev).bfloat16().contiguous(memory_format=CL)
+        res = torch.randn(1, Cc, H, W, generator=g).to(dev).bfloat16().contiguous(memory_format=CL)
+        w = (torch.randn(Cc, Cc, 3, 3, generator=g) * (2.0 / (9 * Cc)) ** 0.5).to(dev).contiguous(memory_format=CL)
+        fp = torch.stack([0.5 + torch.rand(Cc, generator=g), torch.randn(Cc, generator=g), torch.zeros(Cc)]).to(dev)
+        wf = kp.conv3x3_gen_prep_filter(w, 0, x)
+        pack = kp.conv3x3_bnact_pack(w, None, fp)
+        y = torch.empty_like(x)
+
+        def unfused():
+            t = kp.conv3x3_gen_fwd(x, wf, Cc)
+            return kp.bn_apply_fwd(t, res, L.NHWC, 1, Cc, H * W, fp, True, out=y)
+
+        def fused():
+            return kp.conv3x3_bnact_fwd(x, pack, Cc, res, True)
+
+        d = (unfused().float() - fused().float()).abs().max().item()
+        gu, gf = graphed(unfused), graphed(fused)          # GRAPH_CALLS launches per replay: no host time between kernels
+        tu, tf = [], []
+        for _ in range(reps):
+            tu.append(1e3 * window_ms(gu) / GRAPH_CALLS)
+            tf.append(1e3 * window_ms(gf) / GRAPH_CALLS)
+        mu, mf = float(np.median(tu)), float(np.median(tf))
+        rows.append(dict(H=H, W=W, C=Cc, unfused_us=tu, fused_us=tf, max_abs_diff=d,
+                         gen_variant=kp.conv3x3_gen_variant(1, H, W, Cc, Cc)))
+        print("%-22s %-30s %-30s %.3f" % ("1x%dx%dx%d" % (H, W, Cc), "%.1f (%.1f-%.1f)" % (mu, min(tu), max(tu)),
+                                          "%.1f (%.1f-%.1f)" % (mf, min(tf), max(tf)), mf / mu))
+    print(json.dumps({"device": torch.cuda.get_device_name(0), "layers": rows}))
 
 
 def host_time(fn, iters, warmup):
@@ -229,17 +326,26 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--model", choices=("r18", "x39"), default="r18")
-    ap.add_argument("--reps", type=int, default=3, help="x39: how often the off / on children alternate")
-    ap.add_argument("--arm", choices=X39_ARMS, default=None, help="x39: run this one arm here (what a child is started with)")
+    ap.add_argument("--reps", type=int, default=3, help="arm tables and --layers: how often off / on alternate")
+    ap.add_argument("--arm", choices=ARMS, default=None, help="arm tables: run this one arm here (what a child is started with)")
+    ap.add_argument("--convbn", action="store_true", help="r18: the arm table with the fused conv + BatchNorm layers off / on")
+    ap.add_argument("--layers", action="store_true", help="r18: per-layer micro-benchmarks of the fused conv + BatchNorm kernel")
     ap.add_argument("--iters", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=10)
     a = ap.parse_args()
-    if a.model == "x39":
+    if a.model == "x39" and (a.convbn or a.layers):
+        ap.error("--convbn and --layers belong to --model r18 (the x39 table is `--model x39` alone)")
+    if a.convbn and a.layers:
+        ap.error("--convbn and --layers are two measurements: one per call")
+    if a.model == "r18" and a.layers:
+        r18_layers(max(3, a.reps))
+        return
+    if a.model == "x39" or a.convbn or a.arm is not None:
         iters = a.iters or (10 if a.quick else 100)
         if a.arm is not None:
-            print(json.dumps(x39_arm(a.arm, iters, a.warmup)))
+            print(json.dumps(arm_times(a.arm, iters, a.warmup, a.model)))
         else:
-            x39_table(iters, a.warmup, max(3, a.reps))
+            arm_table(iters, a.warmup, max(3, a.reps), a.model)
         return
     it = 5 if a.quick else 30
     result = {"device": torch.cuda.get_device_name(0), "dtype_env": os.environ.get("TSG_DTYPE", "bf16")}

@@ -1,0 +1,290 @@
+"""3x3 convolution + BatchNorm (+ shortcut) (+ ReLU) as one launch at inference (csrc/convbn.hip).
+
+In eval mode a BatchNorm is an affine map of its running statistics, so `conv3x3 -> bn -> (+ residual) -> relu` is
+`relu?(fma(a, conv3x3(x, W), b) + residual)`, and `tsg_conv3x3_bnact_fwd` computes it from the fp32 accumulators of the
+convolution with one rounding, at the store: one launch instead of tsg_conv3x3_gen_fwd (or tsg_conv3x3_c64_fwd) +
+tsg_bn_apply_fwd, one read of x and of the residual and one write of y.  The unfused chain rounds the convolution to
+bf16 first, so the fused result is not bit-equal to it (and is the closer of the two to the fp32 network).
+
+`install_fused_convbn(module)` re-classes, in place, every module that has one of three STRUCTURES (not classes: the
+reference's own network.py built on our furnace is covered as well).  "A 3x3" below is an nn.Conv2d with kernel 3x3,
+stride 1, padding 1, dilation 1, groups 1, zero padding, C_in % 16 == 0 and C_out % 64 == 0:
+  1. `ConvBnRelu`-shaped: `.conv` a 3x3, `has_bn` with `.bn` a BatchNorm, optionally `.relu` (`has_relu`): BiSeNet's
+     attention-refinement 3x3, refines and head 3x3;
+  2. `BasicBlock`-shaped (`conv1 / bn1 / relu / conv2 / bn2 / downsample`, `conv2` a 3x3): `conv2 + bn2 + residual + relu`
+     is fused, and `conv1 + bn1 + relu` where conv1 is a 3x3 too (a stride-2 conv1 runs the stock conv1 and norm_act);
+     the residual is `x` or the block's own `_identity(x)`;
+  3. `Bottleneck`-shaped (`conv1 / bn1 / conv2 / bn2 / conv3 / bn3`): `conv2 + bn2 + relu` where conv2 is a 3x3.
+Parameters, buffers and state-dict keys stay what they were.  The installer returns the number of LAYERS (convolutions)
+it can fuse: a BasicBlock counts 2 or 1.
+
+A re-classed module takes the fused kernel only when all of this holds: the module and its BatchNorms are in eval mode,
+gradients are disabled, the input is a channels_last bf16 HIP tensor under bf16 autocast, the BatchNorms track running
+statistics and have their buffers, the convolution weights are fp32, no module involved has a forward, forward-pre or
+backward hook, the map is not 1x1 (pooled maps stay with vecconv.pooled_layer), `tsg_conv3x3_bnact_supported` takes the
+shape, and a residual has the output's shape, dtype and layout and is 16-byte aligned.  Every other call — training,
+gradients enabled, fp32 (the parity mode stays on the exact kernels), CPU or NCHW input — runs the method it replaced,
+bit for bit.  The kernel writes a new tensor; the input and the residual are never written.
+
+The constants (the filter in the kernel's fragment order and the BatchNorm's a, b with a convolution bias folded in) are
+packed once per layer, device and dtype, and again when the `_version` (or storage) of the convolution's weight or bias
+or of the BatchNorm's weight, bias, running_mean or running_var, or `eps`, has changed: `load_state_dict` and in-place
+writes show in the next call, and any call that finds the module or one of its BatchNorms in train mode drops the packs
+(our SyncBatchNorm moves the running statistics inside a kernel, where no tensor version counts it).  A pack is never built during a graph capture (a stale layer runs its stock path there);
+the warm-up call of InferenceModule.forward builds it.
+
+TSG_CONVBN_FUSED=0|1 (default 0) is read by torchseg_amd.infer.prepare_inference(fuse_convbn=None); the DDP wrapper and
+ddp.install_kernels never install this.
+"""
+import torch
+import torch.nn as nn
+from torch.nn.modules.batchnorm import _BatchNorm
+
+from . import _lib as L
+from . import fusion as _fusion
+from . import kernels as K
+
+
+def _no_hooks(*mods):
+    return not any(m._forward_hooks or m._forward_pre_hooks or m._backward_hooks for m in mods if m is not None)
+
+
+def _is_3x3(conv):
+    return (isinstance(conv, nn.Conv2d) and conv.kernel_size == (3, 3) and conv.stride == (1, 1)
+            and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros"
+            and conv.in_channels % 16 == 0 and conv.out_channels % 64 == 0)
+
+
+def _pair(conv, bn):
+    return _is_3x3(conv) and isinstance(bn, _BatchNorm) and bn.num_features == conv.out_channels
+
+
+def _cbr_layers(m):
+    """the fusable layers of a ConvBnRelu-shaped module: [(conv, bn)] or []"""
+    if not isinstance(m, nn.Module) or not getattr(m, "has_bn", False):
+        return []
+    conv, bn = getattr(m, "conv", None), getattr(m, "bn", None)
+    relu = getattr(m, "relu", None) if getattr(m, "has_relu", False) else None
+    if getattr(m, "has_relu", False) and not isinstance(relu, nn.ReLU):
+        return []
+    return [(conv, bn)] if _pair(conv, bn) and _no_hooks(m, conv, bn, relu) else []
+
+
+def _has(m, *names):
+    return all(hasattr(m, n) for n in names)
+
+
+def _basic_layers(m):
+    if not _has(m, "conv1", "bn1", "relu", "conv2", "bn2", "downsample", "_identity") or hasattr(m, "conv3"):
+        return []
+    if not isinstance(m.conv1, nn.Conv2d) or not isinstance(m.bn1, _BatchNorm) or not isinstance(m.relu, nn.ReLU):
+        return []
+    if not _pair(m.conv2, m.bn2) or m.conv2.in_channels != m.conv1.out_channels:
+        return []
+    if not _no_hooks(m, m.conv1, m.bn1, m.relu, m.conv2, m.bn2, getattr(m, "relu_inplace", None)):
+        return []
+    return ([(m.conv1, m.bn1)] if _pair(m.conv1, m.bn1) else []) + [(m.conv2, m.bn2)]
+
+
+def _bottleneck_layers(m):
+    if not _has(m, "conv1", "bn1", "relu", "conv2", "bn2", "conv3", "bn3", "downsample", "_identity"):
+        return []
+    if not all(isinstance(c, nn.Conv2d) for c in (m.conv1, m.conv3)) or not isinstance(m.relu, nn.ReLU):
+        return []
+    if not all(isinstance(b, _BatchNorm) for b in (m.bn1, m.bn3)) or not _pair(m.conv2, m.bn2):
+        return []
+    if not _no_hooks(m, m.conv1, m.bn1, m.relu, m.conv2, m.bn2, m.conv3, m.bn3, getattr(m, "relu_inplace", None)):
+        return []
+    return [(m.conv2, m.bn2)]
+
+
+def _out_shape(conv, shape):
+    """shape of conv's output for an input of `shape`"""
+    hw = [(n + 2 * p - d * (k - 1) - 1) // s + 1
+          for n, p, d, k, s in zip(shape[2:], conv.padding, conv.dilation, conv.kernel_size, conv.stride)]
+    return (shape[0], conv.out_channels, hw[0], hw[1])
+
+
+def _input_ok(x):
+    return (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 4 and x.dtype == torch.bfloat16
+            and not (x.shape[2] == 1 and x.shape[3] == 1) and torch.is_autocast_enabled()
+            and torch.get_autocast_dtype("cuda") == torch.bfloat16
+            and x.is_contiguous(memory_format=torch.channels_last))
+
+
+class _FusedConvBn:
+    """What the three mixins share: the per-layer pack cache and the gate of a single fused call."""
+
+    tsg_fused_calls = 0                 # calls of tsg_conv3x3_bnact_fwd made for this module
+
+    def _cbn_pack(self, slot, conv, bn, x):
+        """the constants of layer `slot` for x's device and dtype, or None when they are stale and a capture is running"""
+        srcs = (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)
+        stamp = tuple((t._version, t.data_ptr()) if t is not None else None for t in srcs) + (bn.eps,)
+        cache = self.__dict__.setdefault("_tsg_cbn_packs", {})
+        key = (slot, x.device, x.dtype)
+        hit = cache.get(key)
+        if hit is not None and hit[0] == stamp:
+            return hit[1]
+        if torch.cuda.is_current_stream_capturing():
+            return None
+        kp = K.provider()
+        with torch.autocast("cuda", enabled=False):
+            mean = bn.running_mean.float()
+            invstd = torch.rsqrt(bn.running_var.float() + bn.eps)
+            gamma = bn.weight.float() if bn.weight is not None else None
+            beta = bn.bias.float() if bn.bias is not None else None
+            fp = kp.bn_affine(mean, invstd, gamma, beta)
+            pack = kp.conv3x3_bnact_pack(conv.weight, conv.bias, fp)
+        cache[key] = (stamp, pack)
+        return pack
+
+    def _cbn_ready(self, slot, conv, bn, shape, x, mods):
+        """the pack of layer `slot` when a call on an input of `shape` (x's device, dtype and layout) can be fused"""
+        if bn.training:
+            self._cbn_drop()
+            return None
+        if (not bn.track_running_stats or bn.running_mean is None or bn.running_var is None
+                or conv.weight.dtype != torch.float32 or shape[1] != conv.in_channels or (shape[2] == 1 and shape[3] == 1)
+                or not _no_hooks(conv, bn, *mods)):
+            return None
+        if not K.provider().lib.tsg_conv3x3_bnact_supported(L.BF16, shape[0], shape[2], shape[3], conv.in_channels,
+                                                            conv.out_channels):
+            return None
+        return self._cbn_pack(slot, conv, bn, x)
+
+    def _cbn_drop(self):
+        """A training forward of our SyncBatchNorm moves the running statistics inside its kernel, where no tensor version
+        counts it: whenever the module or one of its BatchNorms is found in train mode the packs go, and are rebuilt by
+        the next fused call."""
+        self.__dict__.pop("_tsg_cbn_packs", None)
+
+    def _cbn_gate(self, x):
+        if self.training:
+            self._cbn_drop()
+            return False
+        return (not torch.is_grad_enabled() and not _fusion.CHAIN_ACTIVE and _input_ok(x)
+                and x.data_ptr() % 16 == 0)
+
+    def _cbn_run(self, x, pack, Cout, residual, relu):
+        y = K.provider().conv3x3_bnact_fwd(x, pack, Cout, residual, relu)
+        self.tsg_fused_calls += 1
+        return y
+
+
+def _residual_ok(r, shape, like):
+    """r can be the kernel's residual for an output of `shape` on `like`'s device and of its dtype"""
+    return (isinstance(r, torch.Tensor) and tuple(r.shape) == tuple(shape) and r.dtype == like.dtype
+            and r.device == like.device and r.data_ptr() % 16 == 0 and r.is_contiguous(memory_format=torch.channels_last))
+
+
+def _as_input(t):
+    """the stock layer's output as the kernel reads it: channels_last and 16-byte aligned (a copy only if it is not)"""
+    if t.is_contiguous(memory_format=torch.channels_last) and t.data_ptr() % 16 == 0:
+        return t
+    return t.clone(memory_format=torch.channels_last)
+
+
+class _FusedCbr(_FusedConvBn):
+    """Mixed in front of a ConvBnRelu-shaped module's own class."""
+
+    @_fusion.outside_mode(keeps_chain=True)
+    def forward(self, x):
+        if self._cbn_gate(x) and getattr(self, "has_bn", False):
+            relu = self.relu if getattr(self, "has_relu", False) else None
+            pack = self._cbn_ready("conv", self.conv, self.bn, x.shape, x, (self, relu))
+            if pack is not None:
+                return self._cbn_run(x, pack, self.conv.out_channels, None, relu is not None)
+        return super().forward(x)
+
+
+class _FusedBasicBlock(_FusedConvBn):
+    """Mixed in front of a BasicBlock-shaped module's own class."""
+
+    def forward(self, x):
+        if not self._cbn_gate(x):
+            return super().forward(x)
+        from seg_opr.seg_oprs import norm_act
+        conv1, conv2 = self.conv1, self.conv2
+        tail = getattr(self, "relu_inplace", self.relu)
+        mods = (self, self.relu, tail)
+        if self.bn1.training:
+            self._cbn_drop()
+            return super().forward(x)
+        if isinstance(conv1.padding, str) or not _no_hooks(conv1, self.bn1):
+            return super().forward(x)
+        # everything is decided before the first launch: a decline below runs the replaced method and nothing else
+        mid = _out_shape(conv1, x.shape)
+        pack2 = self._cbn_ready("conv2", conv2, self.bn2, mid, x, mods)
+        if pack2 is None:
+            return super().forward(x)
+        pack1 = None
+        if _pair(conv1, self.bn1):
+            pack1 = self._cbn_ready("conv1", conv1, self.bn1, x.shape, x, mods)
+            if pack1 is None:
+                return super().forward(x)
+        residual = self._identity(x)                       # eval mode: no state moves, the stock method may form it again
+        if not _residual_ok(residual, (mid[0], conv2.out_channels) + tuple(mid[2:]), x):
+            return super().forward(x)
+        if pack1 is not None:
+            out = self._cbn_run(x, pack1, conv1.out_channels, None, True)
+        else:                                              # a stride-2 conv1: the stock layer, bf16 under this autocast
+            out = _as_input(norm_act(self.bn1, self.relu, conv1(x)))
+        return self._cbn_run(out, pack2, conv2.out_channels, residual, True)
+
+
+class _FusedBottleneck(_FusedConvBn):
+    """Mixed in front of a Bottleneck-shaped module's own class."""
+
+    def forward(self, x):
+        if not self._cbn_gate(x) or self.bn1.training or self.bn3.training:
+            return super().forward(x)
+        from seg_opr.seg_oprs import norm_act
+        mods = (self, self.conv1, self.bn1, self.relu, self.conv3, self.bn3, getattr(self, "relu_inplace", None))
+        if isinstance(self.conv1.padding, str):
+            return super().forward(x)
+        mid = _out_shape(self.conv1, x.shape)
+        pack = self._cbn_ready("conv2", self.conv2, self.bn2, mid, x, mods)
+        if pack is None:
+            return super().forward(x)
+        out = _as_input(norm_act(self.bn1, self.relu, self.conv1(x)))      # bf16 under this autocast, of shape `mid`
+        out = self._cbn_run(out, pack, self.conv2.out_channels, None, True)
+        return norm_act(self.bn3, getattr(self, "relu_inplace", self.relu), self.conv3(out), residual=self._identity(x))
+
+
+_CLASSES = {}
+
+
+def _fused_class(cls, mixin):
+    sub = _CLASSES.get((cls, mixin))
+    if sub is None:
+        sub = _CLASSES[(cls, mixin)] = type("Fused" + cls.__name__, (mixin, cls), {"__module__": __name__})
+    return sub
+
+
+def eligible_layers(m):
+    """(mixin, [(conv, bn), ...]) of a module that has one of the three structures, else (None, [])"""
+    for mixin, find in ((_FusedBottleneck, _bottleneck_layers), (_FusedBasicBlock, _basic_layers), (_FusedCbr, _cbr_layers)):
+        layers = find(m)
+        if layers:
+            return mixin, layers
+    return None, []
+
+
+def install_fused_convbn(module):
+    """Re-class, in place, every module of `module` with one of the three structures (see the module docstring); returns
+    how many layers (convolutions) the re-classed modules can fuse."""
+    n = 0
+    for m in module.modules():
+        if isinstance(m, _FusedConvBn):
+            continue
+        mixin, layers = eligible_layers(m)
+        if mixin is not None:
+            m.__class__ = _fused_class(type(m), mixin)
+            n += len(layers)
+    return n
+
+
+def fused_calls(module):
+    """how many launches of the fused kernel the modules below `module` made so far"""
+    return sum(m.tsg_fused_calls for m in module.modules() if isinstance(m, _FusedConvBn))

@@ -87,6 +87,10 @@ upsample overrides.  Controlled by env so train.py needs no edit:
                         the eval-mode BatchNorm (+ shortcut, ReLU) with the depthwise result kept in LDS; training, gradients
                         enabled, CPU and NCHW inputs keep the stock path.  Opt-in: profiles/x39_infer_bench.txt; sepconv.py,
                         csrc/sepconv.hip)
+  TSG_CONVBN_FUSED=0|1  (default 0; read by infer.prepare_inference only, never by this wrapper: with 1 the stride-1 3x3 convolutions
+                        of the ResNet blocks and the 3x3 ConvBnRelu layers run with their eval-mode BatchNorm (+ shortcut, ReLU) as
+                        one launch each at inference, one rounding instead of two; training, gradients enabled, fp32, CPU and NCHW
+                        inputs keep the stock path.  Opt-in: profiles/r18_convbn_infer_bench.txt; convbn.py, csrc/convbn.hip)
   TSG_FORK_MODULES=a,b  (default none; e.g. "spatial_path": direct sub-modules of an unchanged network.py that run on a side HIP
                         stream and are joined where their output is first used — BiSeNet's detail branch beside its context
                         path.  Box-dependent (+1.4 % / -0.2 %), hence opt-in; our own BiSeNet builder: TSG_FORK_SPATIAL=1; fusion.py)

@@ -12,7 +12,10 @@
     streams: TSG_FORK_MODULES is not applied here) and replayed from a static input buffer.  The returned tensor is that
     graph's static output: it is overwritten by the next call with the same shape;
   - fuse_separable=True (default: TSG_SEPCONV_FUSED, 0): Xception's separable units run as one launch each
-    (torchseg_amd.sepconv.install_fused_separable, after the kernel install; csrc/sepconv.hip).  Opt-in.
+    (torchseg_amd.sepconv.install_fused_separable, after the kernel install; csrc/sepconv.hip).  Opt-in;
+  - fuse_convbn=True (default: TSG_CONVBN_FUSED, 0): the stride-1 3x3 convolutions of the ResNet blocks and ConvBnRelu layers
+    run with their BatchNorm, shortcut and ReLU as one launch each (torchseg_amd.convbn.install_fused_convbn, after the
+    kernel install; csrc/convbn.hip).  Opt-in.
 The `+=` / interpolate pre-sum and the ConvBnRelu chain fusions stay gated on autograd as in training (not enabled here).
 """
 import contextlib
@@ -30,7 +33,7 @@ def _compute_dtype(dtype):
 
 
 class InferenceModule(nn.Module):
-    def __init__(self, network, dtype=None, channels_last=None, graph=False, fuse_separable=None):
+    def __init__(self, network, dtype=None, channels_last=None, graph=False, fuse_separable=None, fuse_convbn=None):
         super().__init__()
         from . import ddp
         from .syncbn import convert_syncbn_model
@@ -59,6 +62,12 @@ class InferenceModule(nn.Module):
         if fuse_separable:
             from .sepconv import install_fused_separable
             self.fused_separable = install_fused_separable(self.module)
+        if fuse_convbn is None:
+            fuse_convbn = ddp._env_flag("TSG_CONVBN_FUSED", False)
+        self.fused_convbn = 0
+        if fuse_convbn:
+            from .convbn import install_fused_convbn
+            self.fused_convbn = install_fused_convbn(self.module)
         self.graph = bool(graph)
         self._graphs = {}
 
@@ -101,11 +110,12 @@ class InferenceModule(nn.Module):
         return static_out
 
 
-def prepare_inference(network, dtype=None, channels_last=None, graph=False, fuse_separable=None):
+def prepare_inference(network, dtype=None, channels_last=None, graph=False, fuse_separable=None, fuse_convbn=None):
     """See the module docstring.  `dtype`: torch.bfloat16 or torch.float32 (default: TSG_DTYPE, bf16)."""
     if isinstance(network, InferenceModule):
         return network
-    return InferenceModule(network, dtype=dtype, channels_last=channels_last, graph=graph, fuse_separable=fuse_separable)
+    return InferenceModule(network, dtype=dtype, channels_last=channels_last, graph=graph, fuse_separable=fuse_separable,
+                           fuse_convbn=fuse_convbn)
 
 
 def pending_tail(out):

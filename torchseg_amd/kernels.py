@@ -966,6 +966,66 @@ class HipKernels:
                Cin, Cout, stride, int(bool(relu)), L.stream_ptr(x))
         return y
 
+    # ---- 3x3 convolution + BatchNorm (+ residual) (+ ReLU), inference form (csrc/convbn.hip) ----
+    def conv3x3_bnact_supported(self, x, Cout):
+        """x [B,Cin,H,W] channels_last bf16, 16-byte aligned; Cout output channels of a 3x3 / 1 / 1 convolution"""
+        if (x.dim() != 4 or x.dtype != torch.bfloat16 or x.data_ptr() % 16
+                or not x.is_contiguous(memory_format=torch.channels_last)):
+            return False
+        B, Cin, H, W = x.shape
+        return bool(self.lib.tsg_conv3x3_bnact_supported(L.BF16, B, H, W, Cin, Cout))
+
+    def conv3x3_bnact_row_perm(self):
+        """perm [64]: packed output channel 64 t + q of the filter is channel 64 t + perm[q] of the weight"""
+        perm = (C.c_int * 64)()
+        L.call(self.lib.tsg_conv3x3_bnact_row_perm, perm)
+        return list(perm)
+
+    def conv3x3_bnact_plan(self, B, H, W, Cin, Cout):
+        """(pixel tiles per oc tile, persistent blocks per oc tile, oc tiles, grid, LDS bytes per block) of
+        tsg_conv3x3_bnact_fwd"""
+        out = (C.c_int * 5)()
+        L.call(self.lib.tsg_conv3x3_bnact_plan, B, H, W, Cin, Cout, out)
+        return tuple(out)
+
+    def conv3x3_bnact_pack(self, weight, bias, fp):
+        """weight [Cout,Cin,3,3] (fp32 master or bf16, any layout), bias [Cout] or None, fp = fwd_pack [>=2,Cout] fp32 of
+        tsg_bn_affine -> (wf, ab): the bf16 filter in MFMA fragment order with its output channels permuted as
+        tsg_conv3x3_bnact_fwd reads it, and ab fp32 [2,Cout] with the bias folded in (b += a bias)"""
+        if (weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or weight.dtype not in (torch.float32, torch.bfloat16)
+                or fp.dtype != torch.float32 or fp.dim() != 2 or fp.shape[0] < 2 or fp.shape[1] != weight.shape[0]):
+            raise L.TsgError("conv3x3_bnact_pack: a [Cout,Cin,3,3] fp32 / bf16 weight and a fwd_pack [>=2,Cout] needed")
+        Cout, Cin = weight.shape[0], weight.shape[1]
+        if Cin % 16 or Cout % 64:
+            L.check(-3, "conv3x3_bnact_pack")
+        perm = torch.tensor(self.conv3x3_bnact_row_perm(), dtype=torch.int64)
+        index = (torch.arange(0, Cout, 64).view(-1, 1) + perm.view(1, -1)).reshape(-1).to(weight.device)
+        wp = weight.detach().index_select(0, index).contiguous(memory_format=torch.channels_last)
+        wf = torch.empty(9 * Cout * Cin, dtype=torch.bfloat16, device=weight.device)
+        L.call(self.lib.tsg_conv3x3_gen_prep_filter, wp.data_ptr(), L.dtype_code(wp), wf.data_ptr(), Cout, Cin, 0, 64,
+               L.stream_ptr(wp))
+        ab = torch.empty((2, Cout), dtype=torch.float32, device=weight.device)
+        ab.copy_(fp[:2])
+        if bias is not None:
+            ab[1].addcmul_(ab[0], bias.detach().float())
+        return wf, ab
+
+    def conv3x3_bnact_fwd(self, x, pack, Cout, residual, relu):
+        """x [B,Cin,H,W] bf16 channels_last, pack = conv3x3_bnact_pack(...) -> y [B,Cout,H,W] bf16 channels_last, a new
+        tensor; residual: None or y's twin (never written)"""
+        wf, ab = pack
+        B, Cin, H, W = x.shape
+        if (wf.numel() != 9 * Cin * Cout or wf.dtype != torch.bfloat16 or tuple(ab.shape) != (2, Cout)
+                or ab.dtype != torch.float32 or not ab.is_contiguous()):
+            raise L.TsgError("conv3x3_bnact_fwd: the pack does not belong to this convolution")
+        y = torch.empty((B, Cout, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+        if residual is not None and (residual.shape != y.shape or residual.dtype != y.dtype
+                                     or not residual.is_contiguous(memory_format=torch.channels_last)):
+            raise L.TsgError("conv3x3_bnact_fwd: the residual must have the output's shape, dtype and layout")
+        L.call(self.lib.tsg_conv3x3_bnact_fwd, x.data_ptr(), wf.data_ptr(), ab.data_ptr(), L.ptr(residual), y.data_ptr(),
+               B, H, W, Cin, Cout, int(bool(relu)), L.stream_ptr(x))
+        return y
+
     def sgd_step(self, param, grad, buf, lr, momentum, weight_decay, grad_scale, first):
         L.call(self.lib.tsg_sgd_step, param.data_ptr(), grad.data_ptr(), buf.data_ptr(), param.numel(), float(lr),
                float(momentum), float(weight_decay), float(grad_scale), int(first), L.stream_ptr(param))
