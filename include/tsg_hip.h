@@ -973,6 +973,38 @@ int tsg_conv3x3_bnact_fwd(const void* x, const void* wf, const float* ab, const 
                           int64_t H, int64_t W, int Cin, int Cout, int relu, void* stream);
 
 /* ------------------------------------------------------------------------
+ * 1x1 convolution + BatchNorm (+ residual) (+ ReLU), inference form (csrc/pwbn.hip) — replaces, in eval mode, the chain
+ * 1x1 convolution -> tsg_bn_apply_fwd of Bottleneck.conv1 / conv3 (furnace/base_model/resnet.py:80-101), of the 1x1
+ * `downsample` shortcuts (:21-31) and of the 1x1 ConvBnRelu layers (seg_oprs.py:24-46) by one launch:
+ *   y[b, oh, ow, oc] = bf16( relu?( fma(ab[0][oc], u, ab[1][oc]) + float(residual[b, oh, ow, oc]) ) ),
+ *   u = sum_ci W[oc][ci] * x[b, s*oh, s*ow, ci]   (bf16 operands, fp32 MFMA accumulation),
+ *   OH = (H - 1) / s + 1, OW = (W - 1) / s + 1, s = stride in {1, 2}; padding 0 and groups 1 are the caller's to check.
+ * There is ONE rounding, at the store: the result is not bit-equal to the two-launch chain, which rounds u to bf16 first.
+ * x [B,H,W,Cin], residual (may be NULL) and y [B,OH,OW,Cout]: bf16 channels_last, dense, 16-byte aligned; y must not alias
+ * x or the residual.  The stride-2 sub-sampling is part of the kernel's addressing.  Cin % 64 == 0 and Cout % 64 == 0, both
+ * in [64, 2048]; B, H, W >= 1 and every operand holds less than 2^31 elements (csrc/pwb_geom.h states the plan and limits).
+ * ab: fp32 [2][Cout], 16-byte aligned: rows 0 and 1 of what tsg_bn_affine wrote for the BatchNorm; a convolution bias is
+ *   folded by the caller, ab[1] += ab[0] * bias.
+ * wf: tsg_conv1x1_bnact_filter_bytes(Cin, Cout) = 2 * Cin * Cout bytes (0: channels outside the set), written by
+ *   tsg_conv1x1_bnact_prep_filter from the fp32 weight w [Cout][Cin] (16-byte aligned; rounded to bf16, nearest even) in
+ *   the kernel's fragment order, output channels permuted inside every group of 32 (cbn_row_cout); the layout has one
+ *   definition, pwb_filter_decode of csrc/pwb_geom.h.  A pack is specific to (Cin, Cout).
+ * tsg_conv1x1_bnact_supported: 1 exactly for TSG_BF16 and a shape inside the limits above (host-only; pointer alignment
+ *   is the launcher's TSG_E_ALIGN).
+ * tsg_conv1x1_bnact_plan: out5[0] = pixel tiles of 256 consecutive output pixels (per oc tile), out5[1] = persistent
+ *   blocks per oc tile, out5[2] = oc tiles of 64 output channels, out5[3] = grid = out5[1] * out5[2], out5[4] = bytes of LDS
+ *   per block; the block of slot k walks the pixel tiles k, k + out5[1], ...  A function of the shape alone.
+ * fwd and prep_filter return TSG_E_NULL, then TSG_E_SHAPE, then TSG_E_ALIGN, all before any launch.
+ * No atomics, no sum split across blocks, no device query, no environment switch: bit-identical from launch to launch.
+ * No host synchronisation and no allocation: capturable in a graph. */
+int    tsg_conv1x1_bnact_supported(int dtype, int64_t B, int64_t H, int64_t W, int Cin, int Cout, int stride);
+int    tsg_conv1x1_bnact_plan(int64_t B, int64_t H, int64_t W, int Cin, int Cout, int stride, int* out5);
+size_t tsg_conv1x1_bnact_filter_bytes(int Cin, int Cout);
+int    tsg_conv1x1_bnact_prep_filter(const float* w, void* wf, int Cin, int Cout, void* stream);
+int    tsg_conv1x1_bnact_fwd(const void* x, const void* wf, const float* ab, const void* residual, void* y,
+                             int64_t B, int64_t H, int64_t W, int Cin, int Cout, int stride, int relu, void* stream);
+
+/* ------------------------------------------------------------------------
  * Segmentation head tail (csrc/segtail.hip) — replaces, for an evaluated window, the chain
  * `F.log_softmax(F.interpolate(z, (H, W), mode='bilinear', align_corners=True), dim=1)` of the networks' eval forward,
  * the flip pass, `torch.exp` and the window's `data[...] += score` of furnace/engine/evaluator.py:176-188 / :226-242.

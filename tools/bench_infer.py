@@ -32,6 +32,18 @@ BiSeNet-R18 for a 768 x 1536 image, off / on alternated `--reps` times, every ti
 device events.
 
     python tools/bench_infer.py --model r18 --layers [--reps 3]
+
+--model r18|r50 --pwbn: the arm table for the fused 1x1 convolution + BatchNorm layers (prepare_inference(fuse_pointwise=),
+csrc/pwbn.hip) off and on, with fuse_convbn=True in every one of our arms.  --model r50 is the ResNet-50 backbone alone
+(base_model.resnet50(None, norm_layer=nn.BatchNorm2d)); a call computes its four stage outputs.
+
+    python tools/bench_infer.py --model r50 --pwbn [--quick] [--reps 3]
+
+--pwlayers: per-layer figures of that kernel, CACHE-WARM MICRO-BENCHMARKS as under --layers: the fused call against the
+two launches of the unfused inference path (the vendor library's 1x1 convolution + tsg_bn_apply_fwd with the shortcut and
+ReLU) at 1x1 layer shapes of ResNet-50 and BiSeNet-R18 for a 768 x 1536 image.
+
+    python tools/bench_infer.py --pwlayers [--reps 3]
 """
 import argparse
 import copy
@@ -54,6 +66,12 @@ def r18():
     from torchseg_amd.workloads.bisenet import BiSeNet
     torch.manual_seed(0)
     return BiSeNet(19, False, None, None, nn.BatchNorm2d).eval()
+
+
+def r50():
+    from base_model.resnet import resnet50
+    torch.manual_seed(0)
+    return resnet50(None, norm_layer=nn.BatchNorm2d).eval()
 
 
 def x39():
@@ -80,9 +98,14 @@ def event_times(fn, iters, warmup):
     return [a.elapsed_time(b) for a, b in pairs]
 
 
-# model -> (builder, title, prepare_inference's switch, attribute with the installed count, that count, module of fused_calls)
-ARM_MODELS = {"x39": (x39, "BiSeNet-X39", "fuse_separable", "fused_separable", 51, "sepconv"),
-              "r18": (r18, "BiSeNet-R18", "fuse_convbn", "fused_convbn", 20, "convbn")}
+# table -> (builder, title, prepare_inference's switch, attribute with the installed count, that count, module of fused_calls,
+#           what every one of our arms is prepared with besides)
+ARM_MODELS = {"x39": (x39, "BiSeNet-X39", "fuse_separable", "fused_separable", 51, "sepconv", {}),
+              "r18": (r18, "BiSeNet-R18", "fuse_convbn", "fused_convbn", 20, "convbn", {}),
+              "r18+pwbn": (r18, "BiSeNet-R18, fuse_convbn=True", "fuse_pointwise", "fused_pointwise", 8, "pwbn",
+                           {"fuse_convbn": True}),
+              "r50+pwbn": (r50, "ResNet-50 backbone, fuse_convbn=True", "fuse_pointwise", "fused_pointwise", 36, "pwbn",
+                           {"fuse_convbn": True})}
 
 
 def arm_times(arm, iters, warmup, model="x39"):
@@ -90,7 +113,7 @@ def arm_times(arm, iters, warmup, model="x39"):
     import importlib
     from torchseg_amd.fusion import materialize
     from torchseg_amd.infer import prepare_inference
-    build, _, switch, counter, count, where = ARM_MODELS[model]
+    build, _, switch, counter, count, where, fixed = ARM_MODELS[model]
     fused_calls = importlib.import_module("torchseg_amd." + where).fused_calls
     dev = torch.device("cuda:0")
     net = build().to(dev)
@@ -99,9 +122,11 @@ def arm_times(arm, iters, warmup, model="x39"):
             with torch.no_grad():
                 return net(x)
     else:
-        prep = prepare_inference(net, dtype=torch.bfloat16, graph=arm.startswith("graph"), **{switch: arm.endswith("_on")})
+        prep = prepare_inference(net, dtype=torch.bfloat16, graph=arm.startswith("graph"), **{switch: arm.endswith("_on")},
+                                 **fixed)
         assert getattr(prep, counter) == (count if arm.endswith("_on") else 0)
-        run = (lambda x: prep(x)) if prep.graph else (lambda x: materialize(prep(x)))
+        tensor_out = build is not r50                     # the backbone returns its four stage outputs, all computed
+        run = (lambda x: prep(x)) if prep.graph or not tensor_out else (lambda x: materialize(prep(x)))
     out = {}
     for res in ARM_RES:
         x = torch.randn(1, 3, *res, device=dev)
@@ -116,8 +141,8 @@ def arm_table(iters, warmup, reps, model="x39"):
     title = ARM_MODELS[model][1]
 
     def child(arm):
-        cmd = [sys.executable, os.path.abspath(__file__), "--model", model, "--arm", arm, "--iters", str(iters),
-               "--warmup", str(warmup)]
+        cmd = [sys.executable, os.path.abspath(__file__), "--model", model.split("+")[0], "--arm", arm, "--iters", str(iters),
+               "--warmup", str(warmup)] + (["--pwbn"] if model.endswith("+pwbn") else [])
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
         if r.returncode != 0:
             raise RuntimeError("arm %s failed (%d):\n%s\n%s" % (arm, r.returncode, r.stdout[-2000:], r.stderr[-2000:]))
@@ -233,6 +258,63 @@ def r18_layers(reps):
     print(json.dumps({"device": torch.cuda.get_device_name(0), "layers": rows}))
 
 
+# (H, W, C_in, C_out, stride, shortcut, ReLU) at 768 x 1536: ResNet-50's conv1 / conv3 / downsample of each stage, the dilated
+# networks' 2048 -> 512 reduction on the 1/8 map, BiSeNet-R18's three shortcuts and ffm.conv_1x1
+PW_LAYERS = ((192, 384, 64, 64, 1, False, True), (192, 384, 64, 256, 1, True, True), (192, 384, 256, 64, 1, False, True),
+             (192, 384, 256, 512, 2, False, False), (96, 192, 512, 128, 1, False, True), (96, 192, 128, 512, 1, True, True),
+             (96, 192, 512, 1024, 2, False, False), (48, 96, 1024, 256, 1, False, True), (48, 96, 256, 1024, 1, True, True),
+             (48, 96, 1024, 2048, 2, False, False), (24, 48, 2048, 512, 1, False, True), (24, 48, 512, 2048, 1, True, True),
+             (96, 192, 2048, 512, 1, False, True), (192, 384, 64, 128, 2, False, False), (96, 192, 128, 256, 2, False, False),
+             (48, 96, 256, 512, 2, False, False), (96, 192, 256, 256, 1, False, True))
+
+
+def pw_layers(reps):
+    """conv1x1 -> BatchNorm (-> + shortcut) (-> ReLU): the vendor library's convolution + tsg_bn_apply_fwd against one launch"""
+    from torchseg_amd import _lib as L, kernels as K
+    kp = K.provider()
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(0)
+    CL = torch.channels_last
+    rows = []
+    print("CACHE-WARM MICRO-BENCHMARKS: one layer in a loop on the same tensors (%d calls per graph replay), us per call, median "
+          "of %d windows of >= 0.25 s (min-max), unfused / fused alternated" % (GRAPH_CALLS, reps))
+    print("%-34s %-30s %-30s %-10s %s" % ("layer (H x W, Cin -> Cout / s)", "conv2d + bn_apply_fwd", "conv1x1_bnact_fwd",
+                                          "fused/unf.", "model TB/s of the fused call"))
+    for H, W, Ci, Co, s, with_res, relu in PW_LAYERS:
+        OH, OW = (H - 1) // s + 1, (W - 1) // s + 1
+        x = torch.randn(1, Ci, H, W, generator=g).to(dev).bfloat16().contiguous(memory_format=CL)
+        res = torch.randn(1, Co, OH, OW, generator=g).to(dev).bfloat16().contiguous(memory_format=CL) if with_res else None
+        w = (torch.randn(Co, Ci, 1, 1, generator=g) * (2.0 / Ci) ** 0.5).to(dev)
+        wb = w.bfloat16().contiguous(memory_format=CL)
+        fp = torch.stack([0.5 + torch.rand(Co, generator=g), torch.randn(Co, generator=g), torch.zeros(Co)]).to(dev)
+        pack = kp.conv1x1_bnact_pack(w, None, fp)
+        y = torch.empty((1, Co, OH, OW), dtype=torch.bfloat16, device=dev, memory_format=CL)
+
+        def unfused():
+            t = F.conv2d(x, wb, None, s)
+            return kp.bn_apply_fwd(t, res, L.NHWC, 1, Co, OH * OW, fp, relu, out=y)
+
+        def fused():
+            return kp.conv1x1_bnact_fwd(x, pack, Co, s, res, relu)
+
+        d = (unfused().float() - fused().float()).abs().max().item()
+        gu, gf = graphed(unfused), graphed(fused)          # GRAPH_CALLS launches per replay: no host time between kernels
+        tu, tf = [], []
+        for _ in range(reps):
+            tu.append(1e3 * window_ms(gu) / GRAPH_CALLS)
+            tf.append(1e3 * window_ms(gf) / GRAPH_CALLS)
+        mu, mf = float(np.median(tu)), float(np.median(tf))
+        # the compulsory bytes of DESIGN.md 7's model: the pixels x reads, the residual, y and the filter, once each (the
+        # Cout / 64 re-reads of x and the per-tile re-reads of the filter are meant to come from L2)
+        nbytes = 2 * (OH * OW * Ci + OH * OW * Co * (2 if with_res else 1) + Ci * Co)
+        rows.append(dict(H=H, W=W, Cin=Ci, Cout=Co, stride=s, residual=with_res, relu=relu, unfused_us=tu, fused_us=tf,
+                         max_abs_diff=d, model_bytes=nbytes, plan=kp.conv1x1_bnact_plan(1, H, W, Ci, Co, s)))
+        print("%-34s %-30s %-30s %-10.3f %.2f" % ("%dx%d, %d -> %d / %d%s" % (H, W, Ci, Co, s, " + res" if with_res else ""),
+                                                  "%.1f (%.1f-%.1f)" % (mu, min(tu), max(tu)),
+                                                  "%.1f (%.1f-%.1f)" % (mf, min(tf), max(tf)), mf / mu, nbytes / mf / 1e6))
+    print(json.dumps({"device": torch.cuda.get_device_name(0), "layers": rows}))
+
+
 def host_time(fn, iters, warmup):
     for _ in range(warmup):
         fn()
@@ -325,11 +407,14 @@ def sliding(iters):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
-    ap.add_argument("--model", choices=("r18", "x39"), default="r18")
+    ap.add_argument("--model", choices=("r18", "x39", "r50"), default="r18")
     ap.add_argument("--reps", type=int, default=3, help="arm tables and --layers: how often off / on alternate")
     ap.add_argument("--arm", choices=ARMS, default=None, help="arm tables: run this one arm here (what a child is started with)")
     ap.add_argument("--convbn", action="store_true", help="r18: the arm table with the fused conv + BatchNorm layers off / on")
     ap.add_argument("--layers", action="store_true", help="r18: per-layer micro-benchmarks of the fused conv + BatchNorm kernel")
+    ap.add_argument("--pwbn", action="store_true",
+                    help="r18, r50: the arm table with fuse_convbn=True and the fused 1x1 conv + BatchNorm layers off / on")
+    ap.add_argument("--pwlayers", action="store_true", help="per-layer micro-benchmarks of the fused 1x1 conv + BatchNorm kernel")
     ap.add_argument("--iters", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=10)
     a = ap.parse_args()
@@ -337,15 +422,25 @@ def main():
         ap.error("--convbn and --layers belong to --model r18 (the x39 table is `--model x39` alone)")
     if a.convbn and a.layers:
         ap.error("--convbn and --layers are two measurements: one per call")
+    if a.pwbn and a.model == "x39":
+        ap.error("--pwbn belongs to --model r18 or --model r50")
+    if a.model == "r50" and not (a.pwbn or a.pwlayers):
+        ap.error("--model r50 has the --pwbn arm table (and --pwlayers) only")
+    if sum((a.convbn, a.layers, a.pwbn, a.pwlayers)) > 1:
+        ap.error("--convbn, --layers, --pwbn and --pwlayers are separate measurements: one per call")
+    if a.pwlayers:
+        pw_layers(max(3, a.reps))
+        return
     if a.model == "r18" and a.layers:
         r18_layers(max(3, a.reps))
         return
-    if a.model == "x39" or a.convbn or a.arm is not None:
+    if a.model == "x39" or a.convbn or a.pwbn or a.arm is not None:
         iters = a.iters or (10 if a.quick else 100)
+        table = a.model + ("+pwbn" if a.pwbn else "")
         if a.arm is not None:
-            print(json.dumps(arm_times(a.arm, iters, a.warmup, a.model)))
+            print(json.dumps(arm_times(a.arm, iters, a.warmup, table)))
         else:
-            arm_table(iters, a.warmup, max(3, a.reps), a.model)
+            arm_table(iters, a.warmup, max(3, a.reps), table)
         return
     it = 5 if a.quick else 30
     result = {"device": torch.cuda.get_device_name(0), "dtype_env": os.environ.get("TSG_DTYPE", "bf16")}

@@ -274,13 +274,14 @@ def eligible_layers(m):
 def install_fused_convbn(module):
     """Re-class, in place, every module of `module` with one of the three structures (see the module docstring); returns
     how many layers (convolutions) the re-classed modules can fuse."""
+    from .pwbn import rebased                                # a module pwbn.py re-classed keeps that mixin in front of ours
     n = 0
     for m in module.modules():
         if isinstance(m, _FusedConvBn):
             continue
         mixin, layers = eligible_layers(m)
         if mixin is not None:
-            m.__class__ = _fused_class(type(m), mixin)
+            m.__class__ = rebased(type(m), lambda cls: _fused_class(cls, mixin))
             n += len(layers)
     return n
 

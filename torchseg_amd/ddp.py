@@ -91,6 +91,11 @@ upsample overrides.  Controlled by env so train.py needs no edit:
                         of the ResNet blocks and the 3x3 ConvBnRelu layers run with their eval-mode BatchNorm (+ shortcut, ReLU) as
                         one launch each at inference, one rounding instead of two; training, gradients enabled, fp32, CPU and NCHW
                         inputs keep the stock path.  Opt-in: profiles/r18_convbn_infer_bench.txt; convbn.py, csrc/convbn.hip)
+  TSG_PWBN_FUSED=0|1    (default 0; read by infer.prepare_inference only, never by this wrapper: with 1 the 1x1 convolutions of the
+                        Bottlenecks (conv1, conv3 with the block's shortcut and ReLU), the 1x1 stride-1 / stride-2 shortcuts and the
+                        1x1 ConvBnRelu layers run with their eval-mode BatchNorm as one launch each at inference, one rounding
+                        instead of two; training, gradients enabled, fp32, CPU and NCHW inputs keep the stock path.  Opt-in;
+                        pwbn.py, csrc/pwbn.hip)
   TSG_FORK_MODULES=a,b  (default none; e.g. "spatial_path": direct sub-modules of an unchanged network.py that run on a side HIP
                         stream and are joined where their output is first used — BiSeNet's detail branch beside its context
                         path.  Box-dependent (+1.4 % / -0.2 %), hence opt-in; our own BiSeNet builder: TSG_FORK_SPATIAL=1; fusion.py)

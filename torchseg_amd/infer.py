@@ -15,7 +15,10 @@
     (torchseg_amd.sepconv.install_fused_separable, after the kernel install; csrc/sepconv.hip).  Opt-in;
   - fuse_convbn=True (default: TSG_CONVBN_FUSED, 0): the stride-1 3x3 convolutions of the ResNet blocks and ConvBnRelu layers
     run with their BatchNorm, shortcut and ReLU as one launch each (torchseg_amd.convbn.install_fused_convbn, after the
-    kernel install; csrc/convbn.hip).  Opt-in.
+    kernel install; csrc/convbn.hip).  Opt-in;
+  - fuse_pointwise=True (default: TSG_PWBN_FUSED, 0): the 1x1 convolutions of the Bottlenecks, the 1x1 shortcuts and the 1x1
+    ConvBnRelu layers run with their BatchNorm, shortcut and ReLU as one launch each
+    (torchseg_amd.pwbn.install_fused_pointwise, after convbn's install; csrc/pwbn.hip).  Opt-in.
 The `+=` / interpolate pre-sum and the ConvBnRelu chain fusions stay gated on autograd as in training (not enabled here).
 """
 import contextlib
@@ -33,7 +36,8 @@ def _compute_dtype(dtype):
 
 
 class InferenceModule(nn.Module):
-    def __init__(self, network, dtype=None, channels_last=None, graph=False, fuse_separable=None, fuse_convbn=None):
+    def __init__(self, network, dtype=None, channels_last=None, graph=False, fuse_separable=None, fuse_convbn=None,
+                 fuse_pointwise=None):
         super().__init__()
         from . import ddp
         from .syncbn import convert_syncbn_model
@@ -68,6 +72,12 @@ class InferenceModule(nn.Module):
         if fuse_convbn:
             from .convbn import install_fused_convbn
             self.fused_convbn = install_fused_convbn(self.module)
+        if fuse_pointwise is None:
+            fuse_pointwise = ddp._env_flag("TSG_PWBN_FUSED", False)
+        self.fused_pointwise = 0
+        if fuse_pointwise:
+            from .pwbn import install_fused_pointwise
+            self.fused_pointwise = install_fused_pointwise(self.module)
         self.graph = bool(graph)
         self._graphs = {}
 
@@ -110,12 +120,13 @@ class InferenceModule(nn.Module):
         return static_out
 
 
-def prepare_inference(network, dtype=None, channels_last=None, graph=False, fuse_separable=None, fuse_convbn=None):
+def prepare_inference(network, dtype=None, channels_last=None, graph=False, fuse_separable=None, fuse_convbn=None,
+                      fuse_pointwise=None):
     """See the module docstring.  `dtype`: torch.bfloat16 or torch.float32 (default: TSG_DTYPE, bf16)."""
     if isinstance(network, InferenceModule):
         return network
     return InferenceModule(network, dtype=dtype, channels_last=channels_last, graph=graph, fuse_separable=fuse_separable,
-                           fuse_convbn=fuse_convbn)
+                           fuse_convbn=fuse_convbn, fuse_pointwise=fuse_pointwise)
 
 
 def pending_tail(out):

@@ -1026,6 +1026,62 @@ class HipKernels:
                B, H, W, Cin, Cout, int(bool(relu)), L.stream_ptr(x))
         return y
 
+    # ---- 1x1 convolution + BatchNorm (+ residual) (+ ReLU), inference form (csrc/pwbn.hip) ----
+    def conv1x1_bnact_supported(self, x, Cout, stride=1):
+        """x [B,Cin,H,W] channels_last bf16, 16-byte aligned; Cout output channels of a 1x1 / stride 1 or 2 convolution"""
+        if (x.dim() != 4 or x.dtype != torch.bfloat16 or x.data_ptr() % 16
+                or not x.is_contiguous(memory_format=torch.channels_last)):
+            return False
+        B, Cin, H, W = x.shape
+        return bool(self.lib.tsg_conv1x1_bnact_supported(L.BF16, B, H, W, Cin, Cout, stride))
+
+    def conv1x1_bnact_plan(self, B, H, W, Cin, Cout, stride=1):
+        """(pixel tiles of 256 output pixels, persistent blocks per oc tile, oc tiles, grid, LDS bytes per block) of
+        tsg_conv1x1_bnact_fwd"""
+        out = (C.c_int * 5)()
+        L.call(self.lib.tsg_conv1x1_bnact_plan, B, H, W, Cin, Cout, stride, out)
+        return tuple(out)
+
+    def conv1x1_bnact_pack(self, weight, bias, fp):
+        """weight [Cout,Cin,1,1] or [Cout,Cin] (fp32 master or bf16), bias [Cout] or None, fp = fwd_pack [>=2,Cout] fp32 of
+        tsg_bn_affine -> (wf, ab): the bf16 filter in the order tsg_conv1x1_bnact_fwd reads it (csrc/pwb_geom.h) and ab fp32
+        [2,Cout] with the bias folded in (b += a bias)"""
+        if (weight.dim() not in (2, 4) or (weight.dim() == 4 and tuple(weight.shape[2:]) != (1, 1))
+                or weight.dtype not in (torch.float32, torch.bfloat16)
+                or fp.dtype != torch.float32 or fp.dim() != 2 or fp.shape[0] < 2 or fp.shape[1] != weight.shape[0]):
+            raise L.TsgError("conv1x1_bnact_pack: a [Cout,Cin,1,1] fp32 / bf16 weight and a fwd_pack [>=2,Cout] needed")
+        Cout, Cin = weight.shape[0], weight.shape[1]
+        nbytes = self.lib.tsg_conv1x1_bnact_filter_bytes(Cin, Cout)
+        if not nbytes:
+            L.check(-3, "conv1x1_bnact_pack")
+        w = weight.detach().reshape(Cout, Cin).float().contiguous()      # bf16 -> fp32 -> bf16 is exact
+        wf = torch.empty(nbytes // 2, dtype=torch.bfloat16, device=weight.device)
+        L.call(self.lib.tsg_conv1x1_bnact_prep_filter, w.data_ptr(), wf.data_ptr(), Cin, Cout, L.stream_ptr(w))
+        ab = torch.empty((2, Cout), dtype=torch.float32, device=weight.device)
+        ab.copy_(fp[:2])
+        if bias is not None:
+            ab[1].addcmul_(ab[0], bias.detach().float())
+        return wf, ab
+
+    def conv1x1_bnact_fwd(self, x, pack, Cout, stride, residual, relu):
+        """x [B,Cin,H,W] bf16 channels_last, pack = conv1x1_bnact_pack(...) -> y [B,Cout,OH,OW] bf16 channels_last, a new
+        tensor; residual: None or y's twin (never written)"""
+        wf, ab = pack
+        B, Cin, H, W = x.shape
+        if (wf.numel() != Cin * Cout or wf.dtype != torch.bfloat16 or tuple(ab.shape) != (2, Cout)
+                or ab.dtype != torch.float32 or not ab.is_contiguous()):
+            raise L.TsgError("conv1x1_bnact_fwd: the pack does not belong to this convolution")
+        if stride not in (1, 2):
+            L.check(-3, "conv1x1_bnact_fwd")
+        y = torch.empty((B, Cout, (H - 1) // stride + 1, (W - 1) // stride + 1), dtype=x.dtype, device=x.device,
+                        memory_format=torch.channels_last)
+        if residual is not None and (residual.shape != y.shape or residual.dtype != y.dtype
+                                     or not residual.is_contiguous(memory_format=torch.channels_last)):
+            raise L.TsgError("conv1x1_bnact_fwd: the residual must have the output's shape, dtype and layout")
+        L.call(self.lib.tsg_conv1x1_bnact_fwd, x.data_ptr(), wf.data_ptr(), ab.data_ptr(), L.ptr(residual), y.data_ptr(),
+               B, H, W, Cin, Cout, stride, int(bool(relu)), L.stream_ptr(x))
+        return y
+
     def sgd_step(self, param, grad, buf, lr, momentum, weight_decay, grad_scale, first):
         L.call(self.lib.tsg_sgd_step, param.data_ptr(), grad.data_ptr(), buf.data_ptr(), param.numel(), float(lr),
                float(momentum), float(weight_decay), float(grad_scale), int(first), L.stream_ptr(param))
