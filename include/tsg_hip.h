@@ -973,6 +973,27 @@ int tsg_conv3x3_bnact_fwd(const void* x, const void* wf, const float* ab, const 
                           int64_t H, int64_t W, int Cin, int Cout, int relu, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Dilated 3x3 convolution + BatchNorm (+ residual) (+ ReLU), inference form (csrc/dilbn.hip) — replaces, in eval mode, the
+ * chain tsg_conv3x3_dil_fwd (or the vendor convolution) -> tsg_bn_apply_fwd of Bottleneck.conv2 in layer3 / layer4 of the
+ * PSPNet / PSANet backbones (workloads/pspnet.py::_nostride_dilate) by one launch:
+ *   y[b][oh][ow][oc] = bf16( relu?( fma(ab[0][oc], u, ab[1][oc]) + float(residual[b][oh][ow][oc]) ) ),
+ *   u = sum over (kh, kw, ci) of w[oc][kh][kw][ci] * x[b][oh + d (kh - 1)][ow + d (kw - 1)][ci]   (fp32 MFMA accumulation)
+ * of the 3x3 / stride 1 / padding d / dilation d convolution of bf16 operands, d = dilation in {2, 4}.  Dilation 1 stays
+ * with tsg_conv3x3_bnact_*.  ONE rounding, at the store: not bit-equal to the two-launch chain.
+ * x, residual (may be NULL), y, ab and wf: exactly as for tsg_conv3x3_bnact_fwd, with the same shape limits
+ *   (csrc/cbn_geom.h).  The prepared filter does not depend on the dilation: there is no pack routine of its own.
+ * tsg_conv3x3_dil_bnact_supported: 1 exactly for TSG_BF16, a dilation of 2 or 4 and a shape inside those limits.
+ * tsg_conv3x3_dil_bnact_plan: out5 = {pixel tiles, persistent blocks per oc tile, oc tiles, grid} of
+ *   tsg_conv3x3_bnact_plan for the same shape, and the bytes of LDS per block for this dilation (78,336 / 77,824).
+ * fwd returns TSG_E_NULL, then TSG_E_SHAPE (the dilation included), then TSG_E_ALIGN, all before any launch.
+ * No atomics, no sum split across blocks, no device query, no environment switch: bit-identical from launch to launch.
+ * No host synchronisation and no allocation: capturable in a graph. */
+int tsg_conv3x3_dil_bnact_supported(int dtype, int64_t B, int64_t H, int64_t W, int Cin, int Cout, int dilation);
+int tsg_conv3x3_dil_bnact_plan(int64_t B, int64_t H, int64_t W, int Cin, int Cout, int dilation, int* out5);
+int tsg_conv3x3_dil_bnact_fwd(const void* x, const void* wf, const float* ab, const void* residual, void* y, int64_t B,
+                              int64_t H, int64_t W, int Cin, int Cout, int dilation, int relu, void* stream);
+
+/* ------------------------------------------------------------------------
  * 1x1 convolution + BatchNorm (+ residual) (+ ReLU), inference form (csrc/pwbn.hip) — replaces, in eval mode, the chain
  * 1x1 convolution -> tsg_bn_apply_fwd of Bottleneck.conv1 / conv3 (furnace/base_model/resnet.py:80-101), of the 1x1
  * `downsample` shortcuts (:21-31) and of the 1x1 ConvBnRelu layers (seg_oprs.py:24-46) by one launch:

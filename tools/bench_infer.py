@@ -44,6 +44,19 @@ two launches of the unfused inference path (the vendor library's 1x1 convolution
 ReLU) at 1x1 layer shapes of ResNet-50 and BiSeNet-R18 for a 768 x 1536 image.
 
     python tools/bench_infer.py --pwlayers [--reps 3]
+
+--model r50 --dilbn: the arm table for the fused DILATED 3x3 convolution + BatchNorm layers
+(prepare_inference(fuse_dilated=), csrc/dilbn.hip) off and on, with fuse_convbn=True and fuse_pointwise=True in every one
+of our arms.  The network is the dilated ResNet-50-v1c backbone of PSPNet / PSANet (deep stem of width 64, layer3 / layer4
+at stride 1 and dilation 2 / 4); a call computes its four stage outputs.  The off arm is the code path without the switch.
+
+    python tools/bench_infer.py --model r50 --dilbn [--quick] [--reps 3]
+
+--dillayers: per-layer figures of that kernel, CACHE-WARM MICRO-BENCHMARKS as under --layers, at the three layer shapes of
+the 96 x 192 map (256 -> 256 at dilation 2, 512 -> 512 at 2 and at 4): (a) the vendor library's convolution +
+tsg_bn_apply_fwd, (b) tsg_conv3x3_dil_fwd + tsg_bn_apply_fwd, (c) the fused call, the three alternated.
+
+    python tools/bench_infer.py --dillayers [--reps 3]
 """
 import argparse
 import copy
@@ -72,6 +85,18 @@ def r50():
     from base_model.resnet import resnet50
     torch.manual_seed(0)
     return resnet50(None, norm_layer=nn.BatchNorm2d).eval()
+
+
+def r50d():
+    """the backbone of PSPNet / PSANet: ResNet-50-v1c (deep stem) with layer3 / layer4 at stride 1, dilation 2 / 4"""
+    from functools import partial
+    from base_model.resnet import resnet50
+    from torchseg_amd.workloads.pspnet import _nostride_dilate
+    torch.manual_seed(0)
+    net = resnet50(None, norm_layer=nn.BatchNorm2d, deep_stem=True, stem_width=64)
+    net.layer3.apply(partial(_nostride_dilate, dilate=2))
+    net.layer4.apply(partial(_nostride_dilate, dilate=4))
+    return net.eval()
 
 
 def x39():
@@ -105,7 +130,9 @@ ARM_MODELS = {"x39": (x39, "BiSeNet-X39", "fuse_separable", "fused_separable", 5
               "r18+pwbn": (r18, "BiSeNet-R18, fuse_convbn=True", "fuse_pointwise", "fused_pointwise", 8, "pwbn",
                            {"fuse_convbn": True}),
               "r50+pwbn": (r50, "ResNet-50 backbone, fuse_convbn=True", "fuse_pointwise", "fused_pointwise", 36, "pwbn",
-                           {"fuse_convbn": True})}
+                           {"fuse_convbn": True}),
+              "r50+dilbn": (r50d, "dilated ResNet-50-v1c backbone, fuse_convbn=True, fuse_pointwise=True", "fuse_dilated",
+                            "fused_dilated", 8, "convbn:dil_fused_calls", {"fuse_convbn": True, "fuse_pointwise": True})}
 
 
 def arm_times(arm, iters, warmup, model="x39"):
@@ -114,7 +141,8 @@ def arm_times(arm, iters, warmup, model="x39"):
     from torchseg_amd.fusion import materialize
     from torchseg_amd.infer import prepare_inference
     build, _, switch, counter, count, where, fixed = ARM_MODELS[model]
-    fused_calls = importlib.import_module("torchseg_amd." + where).fused_calls
+    where, _, counter_fn = where.partition(":")
+    fused_calls = getattr(importlib.import_module("torchseg_amd." + where), counter_fn or "fused_calls")
     dev = torch.device("cuda:0")
     net = build().to(dev)
     if arm == "stock_fp32":
@@ -125,7 +153,7 @@ def arm_times(arm, iters, warmup, model="x39"):
         prep = prepare_inference(net, dtype=torch.bfloat16, graph=arm.startswith("graph"), **{switch: arm.endswith("_on")},
                                  **fixed)
         assert getattr(prep, counter) == (count if arm.endswith("_on") else 0)
-        tensor_out = build is not r50                     # the backbone returns its four stage outputs, all computed
+        tensor_out = build not in (r50, r50d)             # the backbone returns its four stage outputs, all computed
         run = (lambda x: prep(x)) if prep.graph or not tensor_out else (lambda x: materialize(prep(x)))
     out = {}
     for res in ARM_RES:
@@ -142,7 +170,7 @@ def arm_table(iters, warmup, reps, model="x39"):
 
     def child(arm):
         cmd = [sys.executable, os.path.abspath(__file__), "--model", model.split("+")[0], "--arm", arm, "--iters", str(iters),
-               "--warmup", str(warmup)] + (["--pwbn"] if model.endswith("+pwbn") else [])
+               "--warmup", str(warmup)] + (["--" + model.split("+")[1]] if "+" in model else [])
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
         if r.returncode != 0:
             raise RuntimeError("arm %s failed (%d):\n%s\n%s" % (arm, r.returncode, r.stdout[-2000:], r.stderr[-2000:]))
@@ -315,6 +343,64 @@ def pw_layers(reps):
     print(json.dumps({"device": torch.cuda.get_device_name(0), "layers": rows}))
 
 
+# (H, W, C, dilation): the middle convolutions of the layer3 / layer4 Bottlenecks of the dilated ResNet-50 / -101 on the 1/8 map
+# of a 768 x 1536 image (5 / 22 layers, 1 layer, 2 layers)
+DIL_LAYERS = ((96, 192, 256, 2), (96, 192, 512, 2), (96, 192, 512, 4))
+
+
+def dil_layers(reps):
+    """dilated conv3x3 -> BatchNorm -> ReLU: (a) the vendor library's convolution + tsg_bn_apply_fwd (the default inference
+    path), (b) tsg_conv3x3_dil_fwd + tsg_bn_apply_fwd (TSG_CONV_DIL=1), (c) one launch"""
+    from torchseg_amd import _lib as L, kernels as K
+    kp = K.provider()
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(0)
+    CL = torch.channels_last
+    rows = []
+    print("CACHE-WARM MICRO-BENCHMARKS: one layer in a loop on the same tensors (%d calls per graph replay), us per call, median "
+          "of %d windows of >= 0.25 s (min-max), the three variants alternated" % (GRAPH_CALLS, reps))
+    print("%-26s %-26s %-26s %-26s %-8s %-8s %s" % ("layer (H x W, C -> C, d)", "(a) conv2d + bn_apply", "(b) dil_fwd + bn_apply",
+                                                     "(c) conv3x3_dil_bnact_fwd", "c / a", "c / b", "model TB/s of (c)"))
+    for H, W, Cc, d in DIL_LAYERS:
+        x = torch.randn(1, Cc, H, W, generator=g).to(dev).bfloat16().contiguous(memory_format=CL)
+        w = (torch.randn(Cc, Cc, 3, 3, generator=g) * (2.0 / (9 * Cc)) ** 0.5).to(dev).contiguous(memory_format=CL)
+        wb = w.bfloat16().contiguous(memory_format=CL)
+        fp = torch.stack([0.5 + torch.rand(Cc, generator=g), torch.randn(Cc, generator=g), torch.zeros(Cc)]).to(dev)
+        wf = kp.conv3x3_dil_prep_filter(w, 0, x)
+        pack = kp.conv3x3_bnact_pack(w, None, fp)
+        y = torch.empty_like(x)
+
+        def vendor():
+            t = F.conv2d(x, wb, None, 1, d, d)
+            return kp.bn_apply_fwd(t, None, L.NHWC, 1, Cc, H * W, fp, True, out=y)
+
+        def ours():
+            t = kp.conv3x3_dil_fwd(x, wf, Cc, d)
+            return kp.bn_apply_fwd(t, None, L.NHWC, 1, Cc, H * W, fp, True, out=y)
+
+        def fused():
+            return kp.conv3x3_dil_bnact_fwd(x, pack, Cc, d, None, True)
+
+        ref = fused().float()
+        da, db = (vendor().float() - ref).abs().max().item(), (ours().float() - ref).abs().max().item()
+        ga, gb, gc = graphed(vendor), graphed(ours), graphed(fused)     # GRAPH_CALLS launches per replay
+        ta, tb, tc = [], [], []
+        for _ in range(reps):
+            ta.append(1e3 * window_ms(ga) / GRAPH_CALLS)
+            tb.append(1e3 * window_ms(gb) / GRAPH_CALLS)
+            tc.append(1e3 * window_ms(gc) / GRAPH_CALLS)
+        ma, mb, mc = float(np.median(ta)), float(np.median(tb)), float(np.median(tc))
+        # the compulsory bytes of DESIGN.md 7's model: x, y and the filter once each (the Cout / 64 re-reads of x, the halo
+        # and the per-tile re-reads of the filter are meant to come from L2)
+        nbytes = 2 * (H * W * Cc * 2 + 9 * Cc * Cc)
+        rows.append(dict(H=H, W=W, C=Cc, dilation=d, vendor_us=ta, dil_fwd_us=tb, fused_us=tc, max_abs_diff_vendor=da,
+                         max_abs_diff_dil_fwd=db, model_bytes=nbytes, plan=kp.conv3x3_dil_bnact_plan(1, H, W, Cc, Cc, d)))
+        cell = lambda m, t: "%.1f (%.1f-%.1f)" % (m, min(t), max(t))
+        print("%-26s %-26s %-26s %-26s %-8.3f %-8.3f %.2f" % ("%dx%d, %d -> %d, d %d" % (H, W, Cc, Cc, d), cell(ma, ta), cell(mb, tb),
+                                                            cell(mc, tc), mc / ma, mc / mb, nbytes / mc / 1e6))
+    print(json.dumps({"device": torch.cuda.get_device_name(0), "layers": rows}))
+
+
 def host_time(fn, iters, warmup):
     for _ in range(warmup):
         fn()
@@ -415,17 +501,29 @@ def main():
     ap.add_argument("--pwbn", action="store_true",
                     help="r18, r50: the arm table with fuse_convbn=True and the fused 1x1 conv + BatchNorm layers off / on")
     ap.add_argument("--pwlayers", action="store_true", help="per-layer micro-benchmarks of the fused 1x1 conv + BatchNorm kernel")
+    ap.add_argument("--dilbn", action="store_true",
+                    help="r50: the arm table of the DILATED ResNet-50-v1c backbone with fuse_convbn=True, fuse_pointwise=True and "
+                         "the fused dilated 3x3 conv + BatchNorm layers off / on")
+    ap.add_argument("--dillayers", action="store_true",
+                    help="per-layer micro-benchmarks of the fused dilated 3x3 conv + BatchNorm kernel")
     ap.add_argument("--iters", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=10)
     a = ap.parse_args()
+    if a.dilbn and a.model != "r50":
+        ap.error("--dilbn belongs to --model r50 (the dilated ResNet-50-v1c backbone)")
+    if sum((a.convbn, a.layers, a.pwbn, a.pwlayers, a.dilbn, a.dillayers)) > 1:
+        ap.error("--convbn, --layers, --pwbn, --pwlayers, --dilbn and --dillayers are separate measurements: one per call")
+    if a.dillayers:
+        dil_layers(max(3, a.reps))
+        return
     if a.model == "x39" and (a.convbn or a.layers):
         ap.error("--convbn and --layers belong to --model r18 (the x39 table is `--model x39` alone)")
     if a.convbn and a.layers:
         ap.error("--convbn and --layers are two measurements: one per call")
     if a.pwbn and a.model == "x39":
         ap.error("--pwbn belongs to --model r18 or --model r50")
-    if a.model == "r50" and not (a.pwbn or a.pwlayers):
-        ap.error("--model r50 has the --pwbn arm table (and --pwlayers) only")
+    if a.model == "r50" and not (a.pwbn or a.pwlayers or a.dilbn):
+        ap.error("--model r50 has the --pwbn and --dilbn arm tables (and --pwlayers, --dillayers) only")
     if sum((a.convbn, a.layers, a.pwbn, a.pwlayers)) > 1:
         ap.error("--convbn, --layers, --pwbn and --pwlayers are separate measurements: one per call")
     if a.pwlayers:
@@ -434,9 +532,9 @@ def main():
     if a.model == "r18" and a.layers:
         r18_layers(max(3, a.reps))
         return
-    if a.model == "x39" or a.convbn or a.pwbn or a.arm is not None:
+    if a.model == "x39" or a.convbn or a.pwbn or a.dilbn or a.arm is not None:
         iters = a.iters or (10 if a.quick else 100)
-        table = a.model + ("+pwbn" if a.pwbn else "")
+        table = a.model + ("+pwbn" if a.pwbn else "+dilbn" if a.dilbn else "")
         if a.arm is not None:
             print(json.dumps(arm_times(a.arm, iters, a.warmup, table)))
         else:

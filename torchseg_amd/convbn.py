@@ -33,8 +33,19 @@ writes show in the next call, and any call that finds the module or one of its B
 (our SyncBatchNorm moves the running statistics inside a kernel, where no tensor version counts it).  A pack is never built during a graph capture (a stale layer runs its stock path there);
 the warm-up call of InferenceModule.forward builds it.
 
-TSG_CONVBN_FUSED=0|1 (default 0) is read by torchseg_amd.infer.prepare_inference(fuse_convbn=None); the DDP wrapper and
-ddp.install_kernels never install this.
+Dilated layers (csrc/dilbn.hip).  `install_fused_convbn(module, dilated=True)` also takes "a 3x3" with
+padding == dilation == 2 or 4 at stride 1: the middle convolution of every Bottleneck of layer3 / layer4 in the PSPNet /
+PSANet backbones (workloads/pspnet.py::_nostride_dilate; 8 layers in R50, 25 in R101).  Such a layer runs
+`tsg_conv3x3_dil_bnact_fwd` instead of the vendor convolution (or `tsg_conv3x3_dil_fwd` under TSG_CONV_DIL=1) +
+`tsg_bn_apply_fwd`; structures, gates, decline rules and the pack cache are the ones above, the filter of the pack does not
+depend on the dilation, and the pack carries the dilation so that `_cbn_run` (and pwbn.py's Bottleneck through it) picks
+the entry point.  `plain=False` re-classes only modules that hold a dilated layer.  Without `dilated=True` nothing about the
+selection changes, and a dilated layer is never fused behind a module installed without it.  `fused_calls` counts the
+launches of both kernels, `dil_fused_calls` those of the dilated one.  The deep stem's 3x3 layers and the stride-2 3x3 layers
+stay unfused.
+
+TSG_CONVBN_FUSED=0|1 (default 0) is read by torchseg_amd.infer.prepare_inference(fuse_convbn=None), TSG_DILBN_FUSED=0|1
+(default 0) by prepare_inference(fuse_dilated=None); the DDP wrapper and ddp.install_kernels never install either.
 """
 import torch
 import torch.nn as nn
@@ -49,17 +60,25 @@ def _no_hooks(*mods):
     return not any(m._forward_hooks or m._forward_pre_hooks or m._backward_hooks for m in mods if m is not None)
 
 
-def _is_3x3(conv):
+_DILATIONS = ((2, 2), (4, 4))           # what csrc/dilbn.hip takes; dilation 1 is csrc/convbn.hip's
+
+
+def _is_3x3(conv, dilated=False):
     return (isinstance(conv, nn.Conv2d) and conv.kernel_size == (3, 3) and conv.stride == (1, 1)
-            and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros"
+            and conv.padding == conv.dilation and (conv.dilation == (1, 1) or (dilated and conv.dilation in _DILATIONS))
+            and conv.groups == 1 and conv.padding_mode == "zeros"
             and conv.in_channels % 16 == 0 and conv.out_channels % 64 == 0)
 
 
-def _pair(conv, bn):
-    return _is_3x3(conv) and isinstance(bn, _BatchNorm) and bn.num_features == conv.out_channels
+def _is_dilated(conv):
+    return _is_3x3(conv, True) and conv.dilation != (1, 1)
 
 
-def _cbr_layers(m):
+def _pair(conv, bn, dilated=False):
+    return _is_3x3(conv, dilated) and isinstance(bn, _BatchNorm) and bn.num_features == conv.out_channels
+
+
+def _cbr_layers(m, dilated=False):
     """the fusable layers of a ConvBnRelu-shaped module: [(conv, bn)] or []"""
     if not isinstance(m, nn.Module) or not getattr(m, "has_bn", False):
         return []
@@ -67,31 +86,31 @@ def _cbr_layers(m):
     relu = getattr(m, "relu", None) if getattr(m, "has_relu", False) else None
     if getattr(m, "has_relu", False) and not isinstance(relu, nn.ReLU):
         return []
-    return [(conv, bn)] if _pair(conv, bn) and _no_hooks(m, conv, bn, relu) else []
+    return [(conv, bn)] if _pair(conv, bn, dilated) and _no_hooks(m, conv, bn, relu) else []
 
 
 def _has(m, *names):
     return all(hasattr(m, n) for n in names)
 
 
-def _basic_layers(m):
+def _basic_layers(m, dilated=False):
     if not _has(m, "conv1", "bn1", "relu", "conv2", "bn2", "downsample", "_identity") or hasattr(m, "conv3"):
         return []
     if not isinstance(m.conv1, nn.Conv2d) or not isinstance(m.bn1, _BatchNorm) or not isinstance(m.relu, nn.ReLU):
         return []
-    if not _pair(m.conv2, m.bn2) or m.conv2.in_channels != m.conv1.out_channels:
+    if not _pair(m.conv2, m.bn2, dilated) or m.conv2.in_channels != m.conv1.out_channels:
         return []
     if not _no_hooks(m, m.conv1, m.bn1, m.relu, m.conv2, m.bn2, getattr(m, "relu_inplace", None)):
         return []
-    return ([(m.conv1, m.bn1)] if _pair(m.conv1, m.bn1) else []) + [(m.conv2, m.bn2)]
+    return ([(m.conv1, m.bn1)] if _pair(m.conv1, m.bn1, dilated) else []) + [(m.conv2, m.bn2)]
 
 
-def _bottleneck_layers(m):
+def _bottleneck_layers(m, dilated=False):
     if not _has(m, "conv1", "bn1", "relu", "conv2", "bn2", "conv3", "bn3", "downsample", "_identity"):
         return []
     if not all(isinstance(c, nn.Conv2d) for c in (m.conv1, m.conv3)) or not isinstance(m.relu, nn.ReLU):
         return []
-    if not all(isinstance(b, _BatchNorm) for b in (m.bn1, m.bn3)) or not _pair(m.conv2, m.bn2):
+    if not all(isinstance(b, _BatchNorm) for b in (m.bn1, m.bn3)) or not _pair(m.conv2, m.bn2, dilated):
         return []
     if not _no_hooks(m, m.conv1, m.bn1, m.relu, m.conv2, m.bn2, m.conv3, m.bn3, getattr(m, "relu_inplace", None)):
         return []
@@ -112,15 +131,21 @@ def _input_ok(x):
             and x.is_contiguous(memory_format=torch.channels_last))
 
 
+class _Pack(tuple):
+    """(wf, ab) of kernels.conv3x3_bnact_pack with the layer's `dilation` as an attribute"""
+
+
 class _FusedConvBn:
     """What the three mixins share: the per-layer pack cache and the gate of a single fused call."""
 
-    tsg_fused_calls = 0                 # calls of tsg_conv3x3_bnact_fwd made for this module
+    tsg_fused_calls = 0                 # calls of tsg_conv3x3_bnact_fwd and tsg_conv3x3_dil_bnact_fwd made for this module
+    tsg_dil_fused_calls = 0             # those of tsg_conv3x3_dil_bnact_fwd among them
+    tsg_cbn_dilated = False             # install_fused_convbn(dilated=True) re-classed this module (_dilated_mixin)
 
     def _cbn_pack(self, slot, conv, bn, x):
         """the constants of layer `slot` for x's device and dtype, or None when they are stale and a capture is running"""
         srcs = (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)
-        stamp = tuple((t._version, t.data_ptr()) if t is not None else None for t in srcs) + (bn.eps,)
+        stamp = tuple((t._version, t.data_ptr()) if t is not None else None for t in srcs) + (bn.eps, conv.dilation[0])
         cache = self.__dict__.setdefault("_tsg_cbn_packs", {})
         key = (slot, x.device, x.dtype)
         hit = cache.get(key)
@@ -135,7 +160,8 @@ class _FusedConvBn:
             gamma = bn.weight.float() if bn.weight is not None else None
             beta = bn.bias.float() if bn.bias is not None else None
             fp = kp.bn_affine(mean, invstd, gamma, beta)
-            pack = kp.conv3x3_bnact_pack(conv.weight, conv.bias, fp)
+            pack = _Pack(kp.conv3x3_bnact_pack(conv.weight, conv.bias, fp))    # the filter does not depend on the dilation
+            pack.dilation = conv.dilation[0]
         cache[key] = (stamp, pack)
         return pack
 
@@ -148,8 +174,14 @@ class _FusedConvBn:
                 or conv.weight.dtype != torch.float32 or shape[1] != conv.in_channels or (shape[2] == 1 and shape[3] == 1)
                 or not _no_hooks(conv, bn, *mods)):
             return None
-        if not K.provider().lib.tsg_conv3x3_bnact_supported(L.BF16, shape[0], shape[2], shape[3], conv.in_channels,
-                                                            conv.out_channels):
+        lib = K.provider().lib
+        if conv.dilation == (1, 1):
+            ok = lib.tsg_conv3x3_bnact_supported(L.BF16, shape[0], shape[2], shape[3], conv.in_channels, conv.out_channels)
+        else:                                   # csrc/dilbn.hip: only behind an install that asked for it
+            ok = (self.tsg_cbn_dilated and _is_dilated(conv)
+                  and lib.tsg_conv3x3_dil_bnact_supported(L.BF16, shape[0], shape[2], shape[3], conv.in_channels,
+                                                          conv.out_channels, conv.dilation[0]))
+        if not ok:
             return None
         return self._cbn_pack(slot, conv, bn, x)
 
@@ -167,7 +199,12 @@ class _FusedConvBn:
                 and x.data_ptr() % 16 == 0)
 
     def _cbn_run(self, x, pack, Cout, residual, relu):
-        y = K.provider().conv3x3_bnact_fwd(x, pack, Cout, residual, relu)
+        d = getattr(pack, "dilation", 1)                   # the pack carries it: callers (pwbn.py too) pass what _cbn_ready gave
+        if d == 1:
+            y = K.provider().conv3x3_bnact_fwd(x, pack, Cout, residual, relu)
+        else:
+            y = K.provider().conv3x3_dil_bnact_fwd(x, pack, Cout, d, residual, relu)
+            self.tsg_dil_fused_calls += 1
         self.tsg_fused_calls += 1
         return y
 
@@ -219,7 +256,7 @@ class _FusedBasicBlock(_FusedConvBn):
         if pack2 is None:
             return super().forward(x)
         pack1 = None
-        if _pair(conv1, self.bn1):
+        if _pair(conv1, self.bn1, self.tsg_cbn_dilated):
             pack1 = self._cbn_ready("conv1", conv1, self.bn1, x.shape, x, mods)
             if pack1 is None:
                 return super().forward(x)
@@ -262,30 +299,53 @@ def _fused_class(cls, mixin):
     return sub
 
 
-def eligible_layers(m):
-    """(mixin, [(conv, bn), ...]) of a module that has one of the three structures, else (None, [])"""
+_DILATED = {}
+
+
+def _dilated_mixin(mixin):
+    """`mixin` as install_fused_convbn(dilated=True) installs it: the same methods, and the dilated layers are taken"""
+    sub = _DILATED.get(mixin)
+    if sub is None:
+        sub = _DILATED[mixin] = type(mixin.__name__ + "Dilated", (mixin,), {"__module__": __name__, "tsg_cbn_dilated": True})
+    return sub
+
+
+def eligible_layers(m, dilated=False):
+    """(mixin, [(conv, bn), ...]) of a module that has one of the three structures, else (None, []); `dilated`: a 3x3 of
+    dilation 2 or 4 (padding alike) counts as well"""
     for mixin, find in ((_FusedBottleneck, _bottleneck_layers), (_FusedBasicBlock, _basic_layers), (_FusedCbr, _cbr_layers)):
-        layers = find(m)
+        layers = find(m, dilated)
         if layers:
-            return mixin, layers
+            return (_dilated_mixin(mixin) if dilated else mixin), layers
     return None, []
 
 
-def install_fused_convbn(module):
+def eligible_dilated_layers(m):
+    """the dilated (2 or 4) layers among eligible_layers(m, dilated=True)[1]: what csrc/dilbn.hip would run"""
+    return [(conv, bn) for conv, bn in eligible_layers(m, True)[1] if _is_dilated(conv)]
+
+
+def install_fused_convbn(module, dilated=False, plain=True):
     """Re-class, in place, every module of `module` with one of the three structures (see the module docstring); returns
-    how many layers (convolutions) the re-classed modules can fuse."""
+    how many layers (convolutions) the re-classed modules can fuse.  `dilated`: layers of dilation 2 and 4 are taken too.
+    `plain=False` (with `dilated`): only modules that hold a dilated layer are re-classed."""
     from .pwbn import rebased                                # a module pwbn.py re-classed keeps that mixin in front of ours
     n = 0
     for m in module.modules():
         if isinstance(m, _FusedConvBn):
             continue
-        mixin, layers = eligible_layers(m)
-        if mixin is not None:
+        mixin, layers = eligible_layers(m, dilated)
+        if mixin is not None and (plain or (dilated and eligible_dilated_layers(m))):
             m.__class__ = rebased(type(m), lambda cls: _fused_class(cls, mixin))
             n += len(layers)
     return n
 
 
 def fused_calls(module):
-    """how many launches of the fused kernel the modules below `module` made so far"""
+    """how many launches of the fused kernels (csrc/convbn.hip and csrc/dilbn.hip) the modules below `module` made so far"""
     return sum(m.tsg_fused_calls for m in module.modules() if isinstance(m, _FusedConvBn))
+
+
+def dil_fused_calls(module):
+    """how many launches of the dilated kernel (csrc/dilbn.hip) alone"""
+    return sum(m.tsg_dil_fused_calls for m in module.modules() if isinstance(m, _FusedConvBn))

@@ -16,6 +16,12 @@
   - fuse_convbn=True (default: TSG_CONVBN_FUSED, 0): the stride-1 3x3 convolutions of the ResNet blocks and ConvBnRelu layers
     run with their BatchNorm, shortcut and ReLU as one launch each (torchseg_amd.convbn.install_fused_convbn, after the
     kernel install; csrc/convbn.hip).  Opt-in;
+  - fuse_dilated=True (default: TSG_DILBN_FUSED, 0): the dilated (2, 4) 3x3 convolutions of the PSPNet / PSANet backbones'
+    layer3 / layer4 Bottlenecks run with their BatchNorm and ReLU as one launch each
+    (torchseg_amd.convbn.install_fused_convbn(dilated=True, plain=False), after fuse_convbn's install and before
+    fuse_pointwise's, on the modules not yet re-classed; csrc/dilbn.hip; the count is `fused_dilated`).  Works with
+    fuse_convbn off: only blocks with a dilated 3x3 are re-classed then.  The deep stem's 3x3 layers and the stride-2 3x3
+    layers stay unfused.  Opt-in: profiles/dilbn_infer_bench.txt;
   - fuse_pointwise=True (default: TSG_PWBN_FUSED, 0): the 1x1 convolutions of the Bottlenecks, the 1x1 shortcuts and the 1x1
     ConvBnRelu layers run with their BatchNorm, shortcut and ReLU as one launch each
     (torchseg_amd.pwbn.install_fused_pointwise, after convbn's install; csrc/pwbn.hip).  Opt-in.
@@ -37,7 +43,7 @@ def _compute_dtype(dtype):
 
 class InferenceModule(nn.Module):
     def __init__(self, network, dtype=None, channels_last=None, graph=False, fuse_separable=None, fuse_convbn=None,
-                 fuse_pointwise=None):
+                 fuse_pointwise=None, fuse_dilated=None):
         super().__init__()
         from . import ddp
         from .syncbn import convert_syncbn_model
@@ -72,6 +78,12 @@ class InferenceModule(nn.Module):
         if fuse_convbn:
             from .convbn import install_fused_convbn
             self.fused_convbn = install_fused_convbn(self.module)
+        if fuse_dilated is None:
+            fuse_dilated = ddp._env_flag("TSG_DILBN_FUSED", False)
+        self.fused_dilated = 0
+        if fuse_dilated:                         # only the modules with a dilated 3x3 that are not re-classed yet
+            from .convbn import install_fused_convbn
+            self.fused_dilated = install_fused_convbn(self.module, dilated=True, plain=False)
         if fuse_pointwise is None:
             fuse_pointwise = ddp._env_flag("TSG_PWBN_FUSED", False)
         self.fused_pointwise = 0
@@ -121,12 +133,12 @@ class InferenceModule(nn.Module):
 
 
 def prepare_inference(network, dtype=None, channels_last=None, graph=False, fuse_separable=None, fuse_convbn=None,
-                      fuse_pointwise=None):
+                      fuse_pointwise=None, fuse_dilated=None):
     """See the module docstring.  `dtype`: torch.bfloat16 or torch.float32 (default: TSG_DTYPE, bf16)."""
     if isinstance(network, InferenceModule):
         return network
     return InferenceModule(network, dtype=dtype, channels_last=channels_last, graph=graph, fuse_separable=fuse_separable,
-                           fuse_convbn=fuse_convbn, fuse_pointwise=fuse_pointwise)
+                           fuse_convbn=fuse_convbn, fuse_pointwise=fuse_pointwise, fuse_dilated=fuse_dilated)
 
 
 def pending_tail(out):
