@@ -193,7 +193,7 @@ confusion_logits:float32 confusion_logits:bfloat16 confusion_logits+out confusio
 seg_tail_logprob:float32 seg_tail_logprob:bfloat16 seg_tail_accum:float32 seg_tail_accum:bfloat16
 seg_tail_accum seg_tail_accum+zflip seg_tail_accum+accumulate seg_tail_accum+zflip+accumulate
 sgd_step sgd_step_dev
-augment_crop augment_crop+gts augment_crop+gts+labels_u8 augment_crop+pad_pixel edge_labels edge_labels+labels_u8
+augment_crop augment_crop+gts augment_crop+gts+labels_u8 augment_crop+pad_pixel augment_crop+pad_pixel+inv_scale edge_labels edge_labels+labels_u8
 """.split()
 
 # launches that take raw addresses in tables: a hand-built guarded test each (test_guarded_gpu.HAND_BUILT)

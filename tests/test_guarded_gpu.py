@@ -76,6 +76,8 @@ def _form(name, args):
             f += "+gts"
         if args["pad_pixel"] >= 0:
             f += "+pad_pixel"
+        if args.get("inv_scale") is not None:
+            f += "+inv_scale"
     labels = [args.get(k) for k in ("labels", "target", "gt")]
     if any(isinstance(v, torch.Tensor) and v.dtype == torch.uint8 for v in labels) or args.get("label_dtype") is torch.uint8:
         f += "+labels_u8"
@@ -181,6 +183,7 @@ def _mods():
     import test_deepstem_gpu, test_dilconv_gpu, test_dwconv_gpu, test_exactconv_gpu, test_pool_gpu, test_stemconv_gpu
     import test_stemfuse_gpu, test_stempool_gpu, test_upsample_gpu, test_vecconv_gpu
     import test_augment_gpu, test_focal_gpu, test_fused_head_gpu, test_metric_gpu, test_ohem_gpu, test_psa_gpu, test_segtail_gpu
+    import test_evalkernels_gpu
     return locals()
 
 
@@ -433,11 +436,13 @@ def upsample_presum(cuda, shape, mp):
 
 
 def resize_hp(cuda, case, mp):
-    """tsg_resize_bilinear_hp has no kernel-level oracle check in the suite to import (the evaluator tests hold it to the
-    oracle end to end): under guard, with the exact relations between its launch forms — out= writes what the plain call
-    returns, and accumulate=True adds the same resize to what `out` held (0 + y)"""
+    """tsg_resize_bilinear_hp under guard: the oracle check of tests/test_evalkernels_gpu.py (resize_scores and torch's
+    float64 interpolate, at that file's bound) at this case's shape, and the exact relations between its launch forms —
+    out= writes what the plain call returns, and accumulate=True adds the same resize to what `out` held (0 + y)"""
     N, C, IH, IW, OH, OW = case
     kp = _kp()
+    for dtype in (torch.float32, torch.bfloat16):
+        _mods()["test_evalkernels_gpu"].test_resize_hp_matches_both_oracles(cuda, dtype, (N * C, IH, IW, OH, OW))
     g = torch.Generator().manual_seed(IH + OW)
     for dtype in (torch.float32, torch.bfloat16):
         x = torch.randn(N, C, IH, IW, generator=g).to(dtype).to(cuda)
@@ -743,6 +748,12 @@ def augment_image_only(cuda, case, mp):
             assert bool((got == float(want)).all()), (c, float(want), got.unique().tolist())
 
 
+def augment_eval_windows(cuda, case, mp):
+    """the form Evaluator.scale_scores launches: inv_scale given, no labels, the raw image padded with 0, every window of
+    the scale in one call, against the oracle's own windows"""
+    _mods()["test_evalkernels_gpu"].test_augment_crop_as_the_evaluator_calls_it(cuda, case)
+
+
 def edge(cuda, case, mp):
     m = _mods()["test_augment_gpu"]
     for label_dtype in (torch.int64, torch.uint8):
@@ -797,6 +808,7 @@ for _dt in (torch.float32, torch.bfloat16):
 _add("sgd", sgd_single, SGD_SIZES, ["sgd_step", "sgd_step_dev"])
 _add("augment", augment, AUG_CASES, ["augment_crop+gts", "augment_crop+gts+labels_u8"])
 _add("augment", augment_image_only, AUG_CASES[:7], ["augment_crop", "augment_crop+pad_pixel", "augment_crop+gts"])
+_add("augment", augment_eval_windows, [((33, 47), 32, 1.25)], ["augment_crop+pad_pixel+inv_scale"])
 _add("augment", edge, EDGE_CASES, ["edge_labels", "edge_labels+labels_u8", "augment_crop+gts", "augment_crop+gts+labels_u8"])
 
 

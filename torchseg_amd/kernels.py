@@ -1522,13 +1522,22 @@ class HipKernels:
         return out
 
     def resize_bilinear_hp(self, x, OH, OW, out=None, accumulate=False):
-        """x [..., IH, IW] f32 / bf16 contiguous -> fp32 [..., OH, OW], half-pixel centres (cv2 INTER_LINEAR on float data)"""
+        """x [..., IH, IW] f32 / bf16 contiguous -> fp32 [..., OH, OW], half-pixel centres (cv2 INTER_LINEAR on float data);
+        out: a contiguous fp32 [..., OH, OW] tensor on x's device to write (accumulate: to add) into.  accumulate without
+        out has nothing to add to and returns the plain result."""
         _require_contiguous(x)
         IH, IW = x.shape[-2], x.shape[-1]
         NC = x.numel() // (IH * IW)
         if out is None:
             out = torch.empty(tuple(x.shape[:-2]) + (OH, OW), dtype=torch.float32, device=x.device)
             accumulate = False
+        else:
+            # the kernel writes NC*OH*OW floats behind out.data_ptr(): anything else is written past its end or mis-laid
+            want = tuple(x.shape[:-2]) + (int(OH), int(OW))
+            if out.dtype != torch.float32 or out.device != x.device or tuple(out.shape) != want or not out.is_contiguous():
+                raise L.TsgError("resize_bilinear_hp: out must be a contiguous float32 %s tensor on %s, got %s %s with "
+                                 "strides %s on %s" % (want, x.device, out.dtype, tuple(out.shape), tuple(out.stride()),
+                                                       out.device))
         L.call(self.lib.tsg_resize_bilinear_hp, x.data_ptr(), out.data_ptr(), L.dtype_code(x), NC, IH, IW, int(OH), int(OW),
                int(accumulate), L.stream_ptr(x))
         return out
