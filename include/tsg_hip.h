@@ -994,6 +994,33 @@ int tsg_conv3x3_dil_bnact_fwd(const void* x, const void* wf, const float* ab, co
                               int64_t H, int64_t W, int Cin, int Cout, int dilation, int relu, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Stride-2 3x3 convolution + BatchNorm (+ residual) (+ ReLU), inference form (csrc/s2bn.hip) — replaces, in eval mode, the
+ * chain vendor convolution (or tsg_conv3x3_c64_s2_fwd) -> tsg_bn_apply_fwd of BasicBlock.conv1 / Bottleneck.conv2 in the
+ * first block of layer2 / 3 / 4 (furnace/base_model/resnet.py) and of the detail branch's 3x3 ConvBnRelu layers
+ * (bisenet SpatialPath) by one launch:
+ *   y[b][oh][ow][oc] = bf16( relu?( fma(ab[0][oc], u, ab[1][oc]) + float(residual[b][oh][ow][oc]) ) ),
+ *   u = sum over (kh, kw, ci) of w[oc][kh][kw][ci] * x[b][2 oh + kh - 1][2 ow + kw - 1][ci]   (fp32 MFMA accumulation)
+ * of the 3x3 / stride 2 / padding 1 / dilation 1 convolution of bf16 operands; OH = (H + 1) / 2, OW = (W + 1) / 2, and
+ * H, W are always the INPUT's.  Stride 1 stays with tsg_conv3x3_bnact_*.  ONE rounding, at the store: not bit-equal to the
+ * two-launch chain.
+ * x [B,H,W,Cin], residual (may be NULL) and y [B,OH,OW,Cout]: bf16 channels_last, dense, 16-byte aligned; y must not alias x
+ * or the residual.  Cin % 16 == 0, Cout % 64 == 0; one image of x (H W Cin) and one of y (OH OW Cout) hold less than 2^31
+ * elements and B * ceil(OH / 4) * ceil(OW / 32) < 2^31 (csrc/s2b_geom.h states the plan and these limits).
+ * ab and wf: exactly as for tsg_conv3x3_bnact_fwd.  The prepared filter (fragment order, tsg_conv3x3_bnact_row_perm) does
+ *   not depend on the stride: there is no pack routine of its own.
+ * tsg_conv3x3_s2_bnact_supported: 1 exactly for TSG_BF16 and a shape inside those limits (host-only).
+ * tsg_conv3x3_s2_bnact_plan: out7 = {OH, OW, pixel tiles of 4 x 32 OUTPUT pixels per oc tile, persistent blocks per oc tile,
+ *   oc tiles, grid, bytes of LDS per block (74,304)}; a block walks the tiles slot, slot + out7[3], ...  A function of the
+ *   shape alone, informational (tests).
+ * fwd returns TSG_E_NULL, then TSG_E_SHAPE, then TSG_E_ALIGN, all before any launch.
+ * No atomics, no sum split across blocks, no device query, no environment switch: bit-identical from launch to launch.
+ * No host synchronisation and no allocation: capturable in a graph. */
+int tsg_conv3x3_s2_bnact_supported(int dtype, int64_t B, int64_t H, int64_t W, int Cin, int Cout);
+int tsg_conv3x3_s2_bnact_plan(int64_t B, int64_t H, int64_t W, int Cin, int Cout, int* out7);
+int tsg_conv3x3_s2_bnact_fwd(const void* x, const void* wf, const float* ab, const void* residual, void* y, int64_t B,
+                             int64_t H, int64_t W, int Cin, int Cout, int relu, void* stream);
+
+/* ------------------------------------------------------------------------
  * 1x1 convolution + BatchNorm (+ residual) (+ ReLU), inference form (csrc/pwbn.hip) — replaces, in eval mode, the chain
  * 1x1 convolution -> tsg_bn_apply_fwd of Bottleneck.conv1 / conv3 (furnace/base_model/resnet.py:80-101), of the 1x1
  * `downsample` shortcuts (:21-31) and of the 1x1 ConvBnRelu layers (seg_oprs.py:24-46) by one launch:

@@ -57,6 +57,19 @@ the 96 x 192 map (256 -> 256 at dilation 2, 512 -> 512 at 2 and at 4): (a) the v
 tsg_bn_apply_fwd, (b) tsg_conv3x3_dil_fwd + tsg_bn_apply_fwd, (c) the fused call, the three alternated.
 
     python tools/bench_infer.py --dillayers [--reps 3]
+
+--model r18|r50 --s2bn: the arm table for the fused STRIDE-2 3x3 convolution + BatchNorm layers
+(prepare_inference(fuse_strided=), csrc/s2bn.hip) off and on, with fuse_convbn=True and fuse_pointwise=True in every one of
+our arms (5 layers in BiSeNet-R18, 3 in the ResNet-50 backbone).  The off arm is the code path without the switch.
+
+    python tools/bench_infer.py --model r18 --s2bn [--quick] [--reps 3]
+
+--s2layers: per-layer figures of that kernel, CACHE-WARM MICRO-BENCHMARKS as under --layers, at the stride-2 layer shapes of
+BiSeNet-R18 and ResNet-50 for a 768 x 1536 image and the detail branch's two layers for 1024 x 2048: (a) the vendor
+library's convolution + tsg_bn_apply_fwd (the inference path without the switch), (b) for 64 -> 64 tsg_conv3x3_c64_s2_fwd +
+tsg_bn_apply_fwd, (c) the fused call, alternated.
+
+    python tools/bench_infer.py --s2layers [--reps 3]
 """
 import argparse
 import copy
@@ -132,7 +145,11 @@ ARM_MODELS = {"x39": (x39, "BiSeNet-X39", "fuse_separable", "fused_separable", 5
               "r50+pwbn": (r50, "ResNet-50 backbone, fuse_convbn=True", "fuse_pointwise", "fused_pointwise", 36, "pwbn",
                            {"fuse_convbn": True}),
               "r50+dilbn": (r50d, "dilated ResNet-50-v1c backbone, fuse_convbn=True, fuse_pointwise=True", "fuse_dilated",
-                            "fused_dilated", 8, "convbn:dil_fused_calls", {"fuse_convbn": True, "fuse_pointwise": True})}
+                            "fused_dilated", 8, "convbn:dil_fused_calls", {"fuse_convbn": True, "fuse_pointwise": True}),
+              "r18+s2bn": (r18, "BiSeNet-R18, fuse_convbn=True, fuse_pointwise=True", "fuse_strided", "fused_strided", 5,
+                           "convbn:s2_fused_calls", {"fuse_convbn": True, "fuse_pointwise": True}),
+              "r50+s2bn": (r50, "ResNet-50 backbone, fuse_convbn=True, fuse_pointwise=True", "fuse_strided", "fused_strided", 3,
+                           "convbn:s2_fused_calls", {"fuse_convbn": True, "fuse_pointwise": True})}
 
 
 def arm_times(arm, iters, warmup, model="x39"):
@@ -401,6 +418,74 @@ def dil_layers(reps):
     print(json.dumps({"device": torch.cuda.get_device_name(0), "layers": rows}))
 
 
+# (H, W, C_in, C_out, image) of the INPUT: the detail branch's two layers and layer2 / 3 / 4's first conv1 of BiSeNet-R18, the
+# first conv2 of layer2 / 3 / 4 of ResNet-50, for a 768 x 1536 image; the detail branch's two layers for 1024 x 2048
+S2_LAYERS = ((384, 768, 64, 64, "768x1536"), (192, 384, 64, 64, "768x1536"), (192, 384, 64, 128, "768x1536"),
+             (96, 192, 128, 256, "768x1536"), (48, 96, 256, 512, "768x1536"), (192, 384, 128, 128, "768x1536"),
+             (96, 192, 256, 256, "768x1536"), (48, 96, 512, 512, "768x1536"), (512, 1024, 64, 64, "1024x2048"),
+             (256, 512, 64, 64, "1024x2048"))
+
+
+def s2_layers(reps):
+    """stride-2 conv3x3 -> BatchNorm -> ReLU: (a) the vendor library's convolution + tsg_bn_apply_fwd (the inference path
+    without the switch), (b) 64 -> 64 only: tsg_conv3x3_c64_s2_fwd + tsg_bn_apply_fwd, (c) one launch"""
+    from torchseg_amd import _lib as L, kernels as K
+    kp = K.provider()
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(0)
+    CL = torch.channels_last
+    rows = []
+    print("CACHE-WARM MICRO-BENCHMARKS: one layer in a loop on the same tensors (%d calls per graph replay), us per call, median "
+          "of %d windows of >= 0.25 s (min-max), the variants alternated" % (GRAPH_CALLS, reps))
+    print("%-36s %-26s %-26s %-26s %-8s %-8s %s" % ("layer (input H x W, Cin -> Cout; image)", "(a) conv2d + bn_apply",
+                                                     "(b) c64_s2_fwd + bn_apply", "(c) conv3x3_s2_bnact_fwd", "c / a", "c / b",
+                                                     "model TB/s of (c)"))
+    for H, W, Ci, Co, image in S2_LAYERS:
+        OH, OW = (H + 1) // 2, (W + 1) // 2
+        x = torch.randn(1, Ci, H, W, generator=g).to(dev).bfloat16().contiguous(memory_format=CL)
+        w = (torch.randn(Co, Ci, 3, 3, generator=g) * (2.0 / (9 * Ci)) ** 0.5).to(dev).contiguous(memory_format=CL)
+        wb = w.bfloat16().contiguous(memory_format=CL)
+        fp = torch.stack([0.5 + torch.rand(Co, generator=g), torch.randn(Co, generator=g), torch.zeros(Co)]).to(dev)
+        pack = kp.conv3x3_bnact_pack(w, None, fp)
+        y = torch.empty((1, Co, OH, OW), dtype=torch.bfloat16, device=dev, memory_format=CL)
+        c64 = Ci == 64 and Co == 64
+
+        def vendor():
+            t = F.conv2d(x, wb, None, 2, 1)
+            return kp.bn_apply_fwd(t, None, L.NHWC, 1, Co, OH * OW, fp, True, out=y)
+
+        def ours():
+            t = kp.conv3x3_c64_fwd(x, wb, stride=2)
+            return kp.bn_apply_fwd(t, None, L.NHWC, 1, Co, OH * OW, fp, True, out=y)
+
+        def fused():
+            return kp.conv3x3_s2_bnact_fwd(x, pack, Co, None, True)
+
+        ref = fused().float()
+        da = (vendor().float() - ref).abs().max().item()
+        db = (ours().float() - ref).abs().max().item() if c64 else None
+        ga, gb, gc = graphed(vendor), graphed(ours) if c64 else None, graphed(fused)    # GRAPH_CALLS launches per replay
+        ta, tb, tc = [], [], []
+        for _ in range(reps):
+            ta.append(1e3 * window_ms(ga) / GRAPH_CALLS)
+            if c64:
+                tb.append(1e3 * window_ms(gb) / GRAPH_CALLS)
+            tc.append(1e3 * window_ms(gc) / GRAPH_CALLS)
+        ma, mc = float(np.median(ta)), float(np.median(tc))
+        mb = float(np.median(tb)) if c64 else None
+        # the compulsory bytes of DESIGN.md 7's model: x, y and the filter once each (the Cout / 64 re-reads of x, the halo
+        # and the per-tile re-reads of the filter are meant to come from L2)
+        nbytes = 2 * (H * W * Ci + OH * OW * Co + 9 * Ci * Co)
+        rows.append(dict(H=H, W=W, Cin=Ci, Cout=Co, image=image, vendor_us=ta, c64_s2_fwd_us=tb, fused_us=tc,
+                         max_abs_diff_vendor=da, max_abs_diff_c64_s2_fwd=db, model_bytes=nbytes,
+                         plan=kp.conv3x3_s2_bnact_plan(1, H, W, Ci, Co)))
+        cell = lambda m, t: "%.1f (%.1f-%.1f)" % (m, min(t), max(t)) if t else "-"
+        print("%-36s %-26s %-26s %-26s %-8.3f %-8s %.2f" % ("%dx%d, %d -> %d; %s" % (H, W, Ci, Co, image), cell(ma, ta), cell(mb, tb),
+                                                             cell(mc, tc), mc / ma, "%.3f" % (mc / mb) if c64 else "-",
+                                                             nbytes / mc / 1e6))
+    print(json.dumps({"device": torch.cuda.get_device_name(0), "layers": rows}))
+
+
 def host_time(fn, iters, warmup):
     for _ in range(warmup):
         fn()
@@ -506,24 +591,35 @@ def main():
                          "the fused dilated 3x3 conv + BatchNorm layers off / on")
     ap.add_argument("--dillayers", action="store_true",
                     help="per-layer micro-benchmarks of the fused dilated 3x3 conv + BatchNorm kernel")
+    ap.add_argument("--s2bn", action="store_true",
+                    help="r18, r50: the arm table with fuse_convbn=True, fuse_pointwise=True and the fused stride-2 3x3 conv + "
+                         "BatchNorm layers off / on")
+    ap.add_argument("--s2layers", action="store_true",
+                    help="per-layer micro-benchmarks of the fused stride-2 3x3 conv + BatchNorm kernel")
     ap.add_argument("--iters", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=10)
     a = ap.parse_args()
     if a.dilbn and a.model != "r50":
         ap.error("--dilbn belongs to --model r50 (the dilated ResNet-50-v1c backbone)")
-    if sum((a.convbn, a.layers, a.pwbn, a.pwlayers, a.dilbn, a.dillayers)) > 1:
-        ap.error("--convbn, --layers, --pwbn, --pwlayers, --dilbn and --dillayers are separate measurements: one per call")
+    if sum((a.convbn, a.layers, a.pwbn, a.pwlayers, a.dilbn, a.dillayers, a.s2bn, a.s2layers)) > 1:
+        ap.error("--convbn, --layers, --pwbn, --pwlayers, --dilbn, --dillayers, --s2bn and --s2layers are separate "
+                 "measurements: one per call")
     if a.dillayers:
         dil_layers(max(3, a.reps))
         return
+    if a.s2layers:
+        s2_layers(max(3, a.reps))
+        return
+    if a.s2bn and a.model == "x39":
+        ap.error("--s2bn belongs to --model r18 or --model r50")
     if a.model == "x39" and (a.convbn or a.layers):
         ap.error("--convbn and --layers belong to --model r18 (the x39 table is `--model x39` alone)")
     if a.convbn and a.layers:
         ap.error("--convbn and --layers are two measurements: one per call")
     if a.pwbn and a.model == "x39":
         ap.error("--pwbn belongs to --model r18 or --model r50")
-    if a.model == "r50" and not (a.pwbn or a.pwlayers or a.dilbn):
-        ap.error("--model r50 has the --pwbn and --dilbn arm tables (and --pwlayers, --dillayers) only")
+    if a.model == "r50" and not (a.pwbn or a.pwlayers or a.dilbn or a.s2bn):
+        ap.error("--model r50 has the --pwbn, --dilbn and --s2bn arm tables (and --pwlayers, --dillayers, --s2layers) only")
     if sum((a.convbn, a.layers, a.pwbn, a.pwlayers)) > 1:
         ap.error("--convbn, --layers, --pwbn and --pwlayers are separate measurements: one per call")
     if a.pwlayers:
@@ -532,9 +628,9 @@ def main():
     if a.model == "r18" and a.layers:
         r18_layers(max(3, a.reps))
         return
-    if a.model == "x39" or a.convbn or a.pwbn or a.dilbn or a.arm is not None:
+    if a.model == "x39" or a.convbn or a.pwbn or a.dilbn or a.s2bn or a.arm is not None:
         iters = a.iters or (10 if a.quick else 100)
-        table = a.model + ("+pwbn" if a.pwbn else "+dilbn" if a.dilbn else "")
+        table = a.model + ("+pwbn" if a.pwbn else "+dilbn" if a.dilbn else "+s2bn" if a.s2bn else "")
         if a.arm is not None:
             print(json.dumps(arm_times(a.arm, iters, a.warmup, table)))
         else:

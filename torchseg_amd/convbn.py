@@ -41,11 +41,29 @@ PSANet backbones (workloads/pspnet.py::_nostride_dilate; 8 layers in R50, 25 in 
 depend on the dilation, and the pack carries the dilation so that `_cbn_run` (and pwbn.py's Bottleneck through it) picks
 the entry point.  `plain=False` re-classes only modules that hold a dilated layer.  Without `dilated=True` nothing about the
 selection changes, and a dilated layer is never fused behind a module installed without it.  `fused_calls` counts the
-launches of both kernels, `dil_fused_calls` those of the dilated one.  The deep stem's 3x3 layers and the stride-2 3x3 layers
-stay unfused.
+launches of all kernels, `dil_fused_calls` those of the dilated one.
+
+Stride-2 layers (csrc/s2bn.hip).  `install_fused_convbn(module, strided=True)` also takes "a 3x3" with stride (2, 2),
+padding (1, 1) and dilation (1, 1) (never stride 2 together with a dilation above 1): BasicBlock.conv1 of the first block
+of layer2 / 3 / 4 and the detail branch's conv_3x3_1 / conv_3x3_2 in BiSeNet-R18 (5 layers), Bottleneck.conv2 of the first
+block of layer2 / 3 / 4 in ResNet-50 / 101 (3 layers; 1 in the dilated PSPNet / PSANet backbones).  Such a layer runs
+`tsg_conv3x3_s2_bnact_fwd` instead of the vendor convolution + `tsg_bn_apply_fwd`, so a whole stride-2 BasicBlock is three
+launches of ours with pwbn's shortcut (conv1 / 2, conv2 + residual, shortcut) and a Bottleneck four (conv1, conv2 / 2,
+conv3, shortcut), in either install order and without a change to pwbn.py: the pack carries the stride (it is part of its
+stamp) and `_cbn_run` picks the entry point.  Structures, gates, decline rules, the pack cache and hook handling are the
+ones above; `_cbn_ready` asks `tsg_conv3x3_s2_bnact_supported` with the INPUT's H and W.  The flag is an attribute of the
+module INSTANCE (`tsg_cbn_strided`; no parameter, buffer or state-dict key): a plain install re-classes BasicBlocks with
+a stride-2 conv1 (their conv2 is eligible), and a later `strided=True` install switches the strided behaviour on for such
+a module, behind pwbn's mixin too, counting its stride-2 layers only.  `plain=False` re-classes or upgrades only modules
+that hold a stride-2 layer (or a dilated one with `dilated=True`).  Without `strided=True` nothing about the selection
+changes, and a stride-2 layer is never fused behind a module installed without it.  `s2_fused_calls` counts the launches
+of the stride-2 kernel.  seg_oprs.cbr_chain (our SpatialPath) runs its modules one after the other when gradients are
+disabled and a link is an eval-mode module with the strided behaviour on, so that the re-classed forward is what runs.
+The deep stem's 3x3 layers stay unfused, as does anything with C_in = 3.
 
 TSG_CONVBN_FUSED=0|1 (default 0) is read by torchseg_amd.infer.prepare_inference(fuse_convbn=None), TSG_DILBN_FUSED=0|1
-(default 0) by prepare_inference(fuse_dilated=None); the DDP wrapper and ddp.install_kernels never install either.
+(default 0) by prepare_inference(fuse_dilated=None), TSG_S2BN_FUSED=0|1 (default 0) by prepare_inference(fuse_strided=None);
+the DDP wrapper and ddp.install_kernels never install any of them.
 """
 import torch
 import torch.nn as nn
@@ -63,22 +81,29 @@ def _no_hooks(*mods):
 _DILATIONS = ((2, 2), (4, 4))           # what csrc/dilbn.hip takes; dilation 1 is csrc/convbn.hip's
 
 
-def _is_3x3(conv, dilated=False):
-    return (isinstance(conv, nn.Conv2d) and conv.kernel_size == (3, 3) and conv.stride == (1, 1)
-            and conv.padding == conv.dilation and (conv.dilation == (1, 1) or (dilated and conv.dilation in _DILATIONS))
+def _is_3x3(conv, dilated=False, strided=False):
+    if not (isinstance(conv, nn.Conv2d) and conv.kernel_size == (3, 3) and conv.padding == conv.dilation
             and conv.groups == 1 and conv.padding_mode == "zeros"
-            and conv.in_channels % 16 == 0 and conv.out_channels % 64 == 0)
+            and conv.in_channels % 16 == 0 and conv.out_channels % 64 == 0):
+        return False
+    if conv.stride == (2, 2):                           # csrc/s2bn.hip: never together with a dilation above 1
+        return strided and conv.dilation == (1, 1)
+    return conv.stride == (1, 1) and (conv.dilation == (1, 1) or (dilated and conv.dilation in _DILATIONS))
 
 
 def _is_dilated(conv):
     return _is_3x3(conv, True) and conv.dilation != (1, 1)
 
 
-def _pair(conv, bn, dilated=False):
-    return _is_3x3(conv, dilated) and isinstance(bn, _BatchNorm) and bn.num_features == conv.out_channels
+def _is_strided(conv):
+    return _is_3x3(conv, False, True) and conv.stride == (2, 2)
 
 
-def _cbr_layers(m, dilated=False):
+def _pair(conv, bn, dilated=False, strided=False):
+    return _is_3x3(conv, dilated, strided) and isinstance(bn, _BatchNorm) and bn.num_features == conv.out_channels
+
+
+def _cbr_layers(m, dilated=False, strided=False):
     """the fusable layers of a ConvBnRelu-shaped module: [(conv, bn)] or []"""
     if not isinstance(m, nn.Module) or not getattr(m, "has_bn", False):
         return []
@@ -86,31 +111,31 @@ def _cbr_layers(m, dilated=False):
     relu = getattr(m, "relu", None) if getattr(m, "has_relu", False) else None
     if getattr(m, "has_relu", False) and not isinstance(relu, nn.ReLU):
         return []
-    return [(conv, bn)] if _pair(conv, bn, dilated) and _no_hooks(m, conv, bn, relu) else []
+    return [(conv, bn)] if _pair(conv, bn, dilated, strided) and _no_hooks(m, conv, bn, relu) else []
 
 
 def _has(m, *names):
     return all(hasattr(m, n) for n in names)
 
 
-def _basic_layers(m, dilated=False):
+def _basic_layers(m, dilated=False, strided=False):
     if not _has(m, "conv1", "bn1", "relu", "conv2", "bn2", "downsample", "_identity") or hasattr(m, "conv3"):
         return []
     if not isinstance(m.conv1, nn.Conv2d) or not isinstance(m.bn1, _BatchNorm) or not isinstance(m.relu, nn.ReLU):
         return []
-    if not _pair(m.conv2, m.bn2, dilated) or m.conv2.in_channels != m.conv1.out_channels:
+    if not _pair(m.conv2, m.bn2, dilated, strided) or m.conv2.in_channels != m.conv1.out_channels:
         return []
     if not _no_hooks(m, m.conv1, m.bn1, m.relu, m.conv2, m.bn2, getattr(m, "relu_inplace", None)):
         return []
-    return ([(m.conv1, m.bn1)] if _pair(m.conv1, m.bn1, dilated) else []) + [(m.conv2, m.bn2)]
+    return ([(m.conv1, m.bn1)] if _pair(m.conv1, m.bn1, dilated, strided) else []) + [(m.conv2, m.bn2)]
 
 
-def _bottleneck_layers(m, dilated=False):
+def _bottleneck_layers(m, dilated=False, strided=False):
     if not _has(m, "conv1", "bn1", "relu", "conv2", "bn2", "conv3", "bn3", "downsample", "_identity"):
         return []
     if not all(isinstance(c, nn.Conv2d) for c in (m.conv1, m.conv3)) or not isinstance(m.relu, nn.ReLU):
         return []
-    if not all(isinstance(b, _BatchNorm) for b in (m.bn1, m.bn3)) or not _pair(m.conv2, m.bn2, dilated):
+    if not all(isinstance(b, _BatchNorm) for b in (m.bn1, m.bn3)) or not _pair(m.conv2, m.bn2, dilated, strided):
         return []
     if not _no_hooks(m, m.conv1, m.bn1, m.relu, m.conv2, m.bn2, m.conv3, m.bn3, getattr(m, "relu_inplace", None)):
         return []
@@ -132,20 +157,24 @@ def _input_ok(x):
 
 
 class _Pack(tuple):
-    """(wf, ab) of kernels.conv3x3_bnact_pack with the layer's `dilation` as an attribute"""
+    """(wf, ab) of kernels.conv3x3_bnact_pack with the layer's `dilation` and `stride` as attributes"""
 
 
 class _FusedConvBn:
     """What the three mixins share: the per-layer pack cache and the gate of a single fused call."""
 
-    tsg_fused_calls = 0                 # calls of tsg_conv3x3_bnact_fwd and tsg_conv3x3_dil_bnact_fwd made for this module
+    tsg_fused_calls = 0                 # calls of tsg_conv3x3_bnact_fwd, _dil_bnact_fwd and _s2_bnact_fwd made for this module
     tsg_dil_fused_calls = 0             # those of tsg_conv3x3_dil_bnact_fwd among them
+    tsg_s2_fused_calls = 0              # those of tsg_conv3x3_s2_bnact_fwd among them
     tsg_cbn_dilated = False             # install_fused_convbn(dilated=True) re-classed this module (_dilated_mixin)
+    tsg_cbn_strided = False             # install_fused_convbn(strided=True) took this module: set on the INSTANCE, so that a
+                                        # module re-classed earlier (by a plain install, behind pwbn's mixin or not) is upgraded
+                                        # without a second re-classing; no parameter, buffer or state-dict key
 
     def _cbn_pack(self, slot, conv, bn, x):
         """the constants of layer `slot` for x's device and dtype, or None when they are stale and a capture is running"""
         srcs = (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)
-        stamp = tuple((t._version, t.data_ptr()) if t is not None else None for t in srcs) + (bn.eps, conv.dilation[0])
+        stamp = tuple((t._version, t.data_ptr()) if t is not None else None for t in srcs) + (bn.eps, conv.dilation[0], conv.stride[0])
         cache = self.__dict__.setdefault("_tsg_cbn_packs", {})
         key = (slot, x.device, x.dtype)
         hit = cache.get(key)
@@ -160,13 +189,13 @@ class _FusedConvBn:
             gamma = bn.weight.float() if bn.weight is not None else None
             beta = bn.bias.float() if bn.bias is not None else None
             fp = kp.bn_affine(mean, invstd, gamma, beta)
-            pack = _Pack(kp.conv3x3_bnact_pack(conv.weight, conv.bias, fp))    # the filter does not depend on the dilation
-            pack.dilation = conv.dilation[0]
+            pack = _Pack(kp.conv3x3_bnact_pack(conv.weight, conv.bias, fp))    # the filter depends on neither
+            pack.dilation, pack.stride = conv.dilation[0], conv.stride[0]
         cache[key] = (stamp, pack)
         return pack
 
     def _cbn_ready(self, slot, conv, bn, shape, x, mods):
-        """the pack of layer `slot` when a call on an input of `shape` (x's device, dtype and layout) can be fused"""
+        """the pack of layer `slot` when a call on an INPUT of `shape` (x's device, dtype and layout) can be fused"""
         if bn.training:
             self._cbn_drop()
             return None
@@ -175,7 +204,11 @@ class _FusedConvBn:
                 or not _no_hooks(conv, bn, *mods)):
             return None
         lib = K.provider().lib
-        if conv.dilation == (1, 1):
+        if conv.stride != (1, 1):               # csrc/s2bn.hip: only behind an install that asked for it; H, W of the input
+            ok = (self.tsg_cbn_strided and _is_strided(conv)
+                  and lib.tsg_conv3x3_s2_bnact_supported(L.BF16, shape[0], shape[2], shape[3], conv.in_channels,
+                                                         conv.out_channels))
+        elif conv.dilation == (1, 1):
             ok = lib.tsg_conv3x3_bnact_supported(L.BF16, shape[0], shape[2], shape[3], conv.in_channels, conv.out_channels)
         else:                                   # csrc/dilbn.hip: only behind an install that asked for it
             ok = (self.tsg_cbn_dilated and _is_dilated(conv)
@@ -200,7 +233,10 @@ class _FusedConvBn:
 
     def _cbn_run(self, x, pack, Cout, residual, relu):
         d = getattr(pack, "dilation", 1)                   # the pack carries it: callers (pwbn.py too) pass what _cbn_ready gave
-        if d == 1:
+        if getattr(pack, "stride", 1) == 2:
+            y = K.provider().conv3x3_s2_bnact_fwd(x, pack, Cout, residual, relu)
+            self.tsg_s2_fused_calls += 1
+        elif d == 1:
             y = K.provider().conv3x3_bnact_fwd(x, pack, Cout, residual, relu)
         else:
             y = K.provider().conv3x3_dil_bnact_fwd(x, pack, Cout, d, residual, relu)
@@ -256,16 +292,16 @@ class _FusedBasicBlock(_FusedConvBn):
         if pack2 is None:
             return super().forward(x)
         pack1 = None
-        if _pair(conv1, self.bn1, self.tsg_cbn_dilated):
+        if _pair(conv1, self.bn1, self.tsg_cbn_dilated, self.tsg_cbn_strided):
             pack1 = self._cbn_ready("conv1", conv1, self.bn1, x.shape, x, mods)
             if pack1 is None:
                 return super().forward(x)
         residual = self._identity(x)                       # eval mode: no state moves, the stock method may form it again
-        if not _residual_ok(residual, (mid[0], conv2.out_channels) + tuple(mid[2:]), x):
+        if not _residual_ok(residual, _out_shape(conv2, mid), x):
             return super().forward(x)
         if pack1 is not None:
             out = self._cbn_run(x, pack1, conv1.out_channels, None, True)
-        else:                                              # a stride-2 conv1: the stock layer, bf16 under this autocast
+        else:                                              # a stride-2 conv1 without `strided`: the stock layer, bf16 here
             out = _as_input(norm_act(self.bn1, self.relu, conv1(x)))
         return self._cbn_run(out, pack2, conv2.out_channels, residual, True)
 
@@ -310,11 +346,11 @@ def _dilated_mixin(mixin):
     return sub
 
 
-def eligible_layers(m, dilated=False):
+def eligible_layers(m, dilated=False, strided=False):
     """(mixin, [(conv, bn), ...]) of a module that has one of the three structures, else (None, []); `dilated`: a 3x3 of
-    dilation 2 or 4 (padding alike) counts as well"""
+    dilation 2 or 4 (padding alike) counts as well; `strided`: one of stride 2 (padding 1, dilation 1) too"""
     for mixin, find in ((_FusedBottleneck, _bottleneck_layers), (_FusedBasicBlock, _basic_layers), (_FusedCbr, _cbr_layers)):
-        layers = find(m, dilated)
+        layers = find(m, dilated, strided)
         if layers:
             return (_dilated_mixin(mixin) if dilated else mixin), layers
     return None, []
@@ -325,27 +361,48 @@ def eligible_dilated_layers(m):
     return [(conv, bn) for conv, bn in eligible_layers(m, True)[1] if _is_dilated(conv)]
 
 
-def install_fused_convbn(module, dilated=False, plain=True):
+def eligible_strided_layers(m):
+    """the stride-2 layers among eligible_layers(m, strided=True)[1]: what csrc/s2bn.hip would run"""
+    return [(conv, bn) for conv, bn in eligible_layers(m, False, True)[1] if _is_strided(conv)]
+
+
+def install_fused_convbn(module, dilated=False, plain=True, strided=False):
     """Re-class, in place, every module of `module` with one of the three structures (see the module docstring); returns
-    how many layers (convolutions) the re-classed modules can fuse.  `dilated`: layers of dilation 2 and 4 are taken too.
-    `plain=False` (with `dilated`): only modules that hold a dilated layer are re-classed."""
+    how many layers (convolutions) become fusable by this call.  `dilated`: layers of dilation 2 and 4 are taken too.
+    `strided`: layers of stride 2 are taken too, and a module re-classed by an earlier call without it is upgraded (its
+    stride-2 layers are what is counted then).  `plain=False` (with `dilated` / `strided`): only modules that hold a dilated
+    / stride-2 layer are re-classed or upgraded."""
     from .pwbn import rebased                                # a module pwbn.py re-classed keeps that mixin in front of ours
     n = 0
     for m in module.modules():
         if isinstance(m, _FusedConvBn):
+            if strided and not m.tsg_cbn_strided:            # the upgrade: the class stays, the stride-2 layers are switched on
+                layers = [cb for cb in eligible_layers(m, m.tsg_cbn_dilated, True)[1] if _is_strided(cb[0])]
+                if layers:
+                    m.__dict__["tsg_cbn_strided"] = True
+                    n += len(layers)
             continue
-        mixin, layers = eligible_layers(m, dilated)
-        if mixin is not None and (plain or (dilated and eligible_dilated_layers(m))):
+        mixin, layers = eligible_layers(m, dilated, strided)
+        if mixin is not None and (plain or (dilated and eligible_dilated_layers(m))
+                                  or (strided and eligible_strided_layers(m))):
             m.__class__ = rebased(type(m), lambda cls: _fused_class(cls, mixin))
+            if strided:
+                m.__dict__["tsg_cbn_strided"] = True
             n += len(layers)
     return n
 
 
 def fused_calls(module):
-    """how many launches of the fused kernels (csrc/convbn.hip and csrc/dilbn.hip) the modules below `module` made so far"""
+    """how many launches of the fused kernels (csrc/convbn.hip, csrc/dilbn.hip and csrc/s2bn.hip) the modules below `module`
+    made so far"""
     return sum(m.tsg_fused_calls for m in module.modules() if isinstance(m, _FusedConvBn))
 
 
 def dil_fused_calls(module):
     """how many launches of the dilated kernel (csrc/dilbn.hip) alone"""
     return sum(m.tsg_dil_fused_calls for m in module.modules() if isinstance(m, _FusedConvBn))
+
+
+def s2_fused_calls(module):
+    """how many launches of the stride-2 kernel (csrc/s2bn.hip) alone"""
+    return sum(m.tsg_s2_fused_calls for m in module.modules() if isinstance(m, _FusedConvBn))

@@ -88,7 +88,15 @@ def cbr_chain(mods, x):
     Between two of them the BatchNorm + ReLU of the first is handed to the convolution of the second
     (torchseg_amd.convwrw.bn_relu_conv: applied while that convolution loads its input when both are on the HIP path, the
     plain module sequence otherwise); results are those of calling the modules one after the other."""
-    if not (x.is_cuda and all(isinstance(m, ConvBnRelu) and m.has_bn and m.has_relu for m in mods[:-1])):
+    # A link that torchseg_amd.convbn.install_fused_convbn(strided=True) took (SpatialPath's two stride-2 3x3 layers) fuses in
+    # its re-classed `forward`, which the direct path below never calls.  With gradients disabled that path is exactly the
+    # modules' own kernels anyway -- stem_bn_relu_conv returns None and bn_relu_conv runs `conv(norm_act(bn, relu, x))`
+    # unless torch.is_grad_enabled() (torchseg_amd/convwrw.py: both conditions name it) -- so the module sequence is run
+    # instead.  No call without such an install changes; with one, every link goes through its module, the last one (a 1x1
+    # that pwbn.install_fused_pointwise may have taken) included.
+    strided = (not torch.is_grad_enabled()
+               and any(getattr(m, "tsg_cbn_strided", False) and not m.training for m in mods))
+    if strided or not (x.is_cuda and all(isinstance(m, ConvBnRelu) and m.has_bn and m.has_relu for m in mods[:-1])):
         for m in mods:
             x = m(x)
         return x

@@ -20,8 +20,15 @@
     layer3 / layer4 Bottlenecks run with their BatchNorm and ReLU as one launch each
     (torchseg_amd.convbn.install_fused_convbn(dilated=True, plain=False), after fuse_convbn's install and before
     fuse_pointwise's, on the modules not yet re-classed; csrc/dilbn.hip; the count is `fused_dilated`).  Works with
-    fuse_convbn off: only blocks with a dilated 3x3 are re-classed then.  The deep stem's 3x3 layers and the stride-2 3x3
-    layers stay unfused.  Opt-in: profiles/dilbn_infer_bench.txt;
+    fuse_convbn off: only blocks with a dilated 3x3 are re-classed then.  Opt-in: profiles/dilbn_infer_bench.txt;
+  - fuse_strided=True (default: TSG_S2BN_FUSED, 0): the stride-2 3x3 convolutions (BasicBlock.conv1 / Bottleneck.conv2 of
+    the first block of layer2 / 3 / 4, the detail branch's conv_3x3_1 / conv_3x3_2) run with their BatchNorm and ReLU as one
+    launch each (torchseg_amd.convbn.install_fused_convbn(strided=True, plain=False), after fuse_dilated's install and
+    before fuse_pointwise's: modules not yet re-classed that hold such a layer are re-classed, modules fuse_convbn
+    re-classed are upgraded; csrc/s2bn.hip; `fused_strided` is the number of stride-2 LAYERS taken: 5 for BiSeNet-R18 with
+    or without fuse_convbn, 3 for ResNet-50, 1 for PSPNet-R50).  With it our SpatialPath runs its ConvBnRelu modules one
+    after the other (seg_oprs.cbr_chain), so its conv_1x1 goes through its module and is fused by fuse_pointwise.  The
+    deep stem's 3x3 layers stay unfused, as does anything with C_in = 3.  Opt-in: profiles/s2bn_infer_bench.txt;
   - fuse_pointwise=True (default: TSG_PWBN_FUSED, 0): the 1x1 convolutions of the Bottlenecks, the 1x1 shortcuts and the 1x1
     ConvBnRelu layers run with their BatchNorm, shortcut and ReLU as one launch each
     (torchseg_amd.pwbn.install_fused_pointwise, after convbn's install; csrc/pwbn.hip).  Opt-in.
@@ -43,7 +50,7 @@ def _compute_dtype(dtype):
 
 class InferenceModule(nn.Module):
     def __init__(self, network, dtype=None, channels_last=None, graph=False, fuse_separable=None, fuse_convbn=None,
-                 fuse_pointwise=None, fuse_dilated=None):
+                 fuse_pointwise=None, fuse_dilated=None, fuse_strided=None):
         super().__init__()
         from . import ddp
         from .syncbn import convert_syncbn_model
@@ -84,6 +91,14 @@ class InferenceModule(nn.Module):
         if fuse_dilated:                         # only the modules with a dilated 3x3 that are not re-classed yet
             from .convbn import install_fused_convbn
             self.fused_dilated = install_fused_convbn(self.module, dilated=True, plain=False)
+        if fuse_strided is None:
+            fuse_strided = ddp._env_flag("TSG_S2BN_FUSED", False)
+        self.fused_strided = 0
+        if fuse_strided:                         # the stride-2 LAYERS: of modules re-classed above (upgraded) and of new ones
+            from .convbn import eligible_strided_layers, install_fused_convbn
+            install_fused_convbn(self.module, strided=True, plain=False)
+            self.fused_strided = sum(len(eligible_strided_layers(m)) for m in self.module.modules()
+                                     if getattr(m, "tsg_cbn_strided", False))
         if fuse_pointwise is None:
             fuse_pointwise = ddp._env_flag("TSG_PWBN_FUSED", False)
         self.fused_pointwise = 0
@@ -133,12 +148,13 @@ class InferenceModule(nn.Module):
 
 
 def prepare_inference(network, dtype=None, channels_last=None, graph=False, fuse_separable=None, fuse_convbn=None,
-                      fuse_pointwise=None, fuse_dilated=None):
+                      fuse_pointwise=None, fuse_dilated=None, fuse_strided=None):
     """See the module docstring.  `dtype`: torch.bfloat16 or torch.float32 (default: TSG_DTYPE, bf16)."""
     if isinstance(network, InferenceModule):
         return network
     return InferenceModule(network, dtype=dtype, channels_last=channels_last, graph=graph, fuse_separable=fuse_separable,
-                           fuse_convbn=fuse_convbn, fuse_pointwise=fuse_pointwise, fuse_dilated=fuse_dilated)
+                           fuse_convbn=fuse_convbn, fuse_pointwise=fuse_pointwise, fuse_dilated=fuse_dilated,
+                           fuse_strided=fuse_strided)
 
 
 def pending_tail(out):

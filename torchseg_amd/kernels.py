@@ -1058,6 +1058,39 @@ class HipKernels:
                B, H, W, Cin, Cout, int(dilation), int(bool(relu)), L.stream_ptr(x))
         return y
 
+    # ---- stride-2 3x3 convolution + BatchNorm (+ residual) (+ ReLU), inference form (csrc/s2bn.hip) ----
+    def conv3x3_s2_bnact_supported(self, x, Cout):
+        """x [B,Cin,H,W] channels_last bf16, 16-byte aligned; Cout output channels of a 3x3 / stride 2 / padding 1 convolution"""
+        if (x.dim() != 4 or x.dtype != torch.bfloat16 or x.data_ptr() % 16
+                or not x.is_contiguous(memory_format=torch.channels_last)):
+            return False
+        B, Cin, H, W = x.shape
+        return bool(self.lib.tsg_conv3x3_s2_bnact_supported(L.BF16, B, H, W, Cin, Cout))
+
+    def conv3x3_s2_bnact_plan(self, B, H, W, Cin, Cout):
+        """(OH, OW, pixel tiles per oc tile, persistent blocks per oc tile, oc tiles, grid, LDS bytes per block) of
+        tsg_conv3x3_s2_bnact_fwd; H, W are the input's"""
+        out = (C.c_int * 7)()
+        L.call(self.lib.tsg_conv3x3_s2_bnact_plan, B, H, W, Cin, Cout, out)
+        return tuple(out)
+
+    def conv3x3_s2_bnact_fwd(self, x, pack, Cout, residual, relu):
+        """x [B,Cin,H,W] bf16 channels_last, pack = conv3x3_bnact_pack(...) (the filter does not depend on the stride) ->
+        y [B,Cout,(H+1)//2,(W+1)//2] bf16 channels_last, a new tensor; residual: None or y's twin (never written)"""
+        wf, ab = pack
+        B, Cin, H, W = x.shape
+        if (wf.numel() != 9 * Cin * Cout or wf.dtype != torch.bfloat16 or tuple(ab.shape) != (2, Cout)
+                or ab.dtype != torch.float32 or not ab.is_contiguous()):
+            raise L.TsgError("conv3x3_s2_bnact_fwd: the pack does not belong to this convolution")
+        y = torch.empty((B, Cout, (H + 1) // 2, (W + 1) // 2), dtype=x.dtype, device=x.device,
+                        memory_format=torch.channels_last)
+        if residual is not None and (residual.shape != y.shape or residual.dtype != y.dtype
+                                     or not residual.is_contiguous(memory_format=torch.channels_last)):
+            raise L.TsgError("conv3x3_s2_bnact_fwd: the residual must have the output's shape, dtype and layout")
+        L.call(self.lib.tsg_conv3x3_s2_bnact_fwd, x.data_ptr(), wf.data_ptr(), ab.data_ptr(), L.ptr(residual), y.data_ptr(),
+               B, H, W, Cin, Cout, int(bool(relu)), L.stream_ptr(x))
+        return y
+
     # ---- 1x1 convolution + BatchNorm (+ residual) (+ ReLU), inference form (csrc/pwbn.hip) ----
     def conv1x1_bnact_supported(self, x, Cout, stride=1):
         """x [B,Cin,H,W] channels_last bf16, 16-byte aligned; Cout output channels of a 1x1 / stride 1 or 2 convolution"""
