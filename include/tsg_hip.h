@@ -263,6 +263,33 @@ int tsg_stem3_conv_fwd(const void* x, const float* w, void* y, int64_t B, int64_
                        void* ws, size_t ws_bytes, void* stream);
 int tsg_stem3_conv_wrw(const void* x, const void* dy, float* dw, int64_t B, int64_t H, int64_t W,
                        void* ws, size_t ws_bytes, void* stream);
+/* The two image convolutions + BatchNorm (+ ReLU), inference form (csrc/stemconv.hip stem_bnact_fwd_k, csrc/deepstem.hip
+ * ds_bnact_fwd_k) — replace, in eval mode, the chain tsg_stem_conv_fwd / tsg_stem3_conv_fwd (or the vendor convolution)
+ * -> tsg_bn_apply_fwd of BiSeNet's SpatialPath.conv_7x7 (a ConvBnRelu) and of the first layer of the ResNet-v1c deep
+ * stem (ResNet._stem c[0], c[1], c[2]) by one launch:
+ *   y[b][oh][ow][oc] = bf16( relu?( fma(ab[0][oc], u, ab[1][oc]) ) ),  u = the fp32 MFMA accumulator of the unfused kernel
+ * (the same tiles, operands and order of accumulation as tsg_stem_conv_fwd / tsg_stem3_conv_fwd).  ONE rounding, at the
+ * store: not bit-equal to the two-launch chain.
+ * x [B,3,H,W] bf16 NCHW, aligned as the unfused entry point asks (4 bytes for the 7x7, which also needs W even; 2 bytes
+ * for the 3x3); y [B,OH,OW,64] bf16 channels_last, OH = (H-1)/2+1, 16-byte aligned.
+ * ab: fp32 [2][64], 16-byte aligned: rows 0 and 1 of what tsg_bn_affine wrote for the BatchNorm.
+ * wp: X_bnact_filter_bytes() bytes (64*176*2 for the 7x7, 64*32*2 for the 3x3), 16-byte aligned, written by X_bnact_pack
+ *   from the fp32 weight [64,3,7,7] / [64,3,3,3] in the layout the unfused kernels build in their workspace on every
+ *   call: here it is packed ONCE per layer, the forward launches one kernel.
+ * X_bnact_supported: 1 exactly for TSG_BF16 and a (B, H, W) the unfused entry point takes (host-only).
+ * pack returns TSG_E_NULL, then TSG_E_ALIGN; fwd TSG_E_NULL, then TSG_E_SHAPE, then TSG_E_ALIGN; all before any launch.
+ * No atomics, no statistics, no workspace, no host synchronisation, no allocation: bit-identical from launch to launch,
+ * capturable in a graph. */
+int tsg_stem_conv_bnact_supported(int dtype, int64_t B, int64_t H, int64_t W);
+size_t tsg_stem_conv_bnact_filter_bytes(void);
+int tsg_stem_conv_bnact_pack(const float* w, void* wp, void* stream);
+int tsg_stem_conv_bnact_fwd(const void* x, const void* wp, const float* ab, void* y, int64_t B, int64_t H, int64_t W,
+                            int relu, void* stream);
+int tsg_stem3_conv_bnact_supported(int dtype, int64_t B, int64_t H, int64_t W);
+size_t tsg_stem3_conv_bnact_filter_bytes(void);
+int tsg_stem3_conv_bnact_pack(const float* w, void* wp, void* stream);
+int tsg_stem3_conv_bnact_fwd(const void* x, const void* wp, const float* ab, void* y, int64_t B, int64_t H, int64_t W,
+                             int relu, void* stream);
 /* The weight gradient with the BatchNorm + ReLU backward of the layer behind the stem folded into its staging: instead
  * of dy it takes da (gradient w.r.t. relu(bn(xc))), the stem's own output xc and the backward pack bp[5][64] of
  * tsg_bn_bwd_coeffs, and evaluates dy = a dv + Bc (xc - mean) + C2, dv = [a xc + b > 0] da (tsg_bn_bwd_apply's

@@ -70,6 +70,21 @@ library's convolution + tsg_bn_apply_fwd (the inference path without the switch)
 tsg_bn_apply_fwd, (c) the fused call, alternated.
 
     python tools/bench_infer.py --s2layers [--reps 3]
+
+--model r18|r50 --stembn: the arm table for the fused image stems and deep stem (prepare_inference(fuse_stem=),
+torchseg_amd/stembn.py) off and on, with every other fusion (fuse_convbn, fuse_dilated, fuse_strided, fuse_pointwise) on in
+every one of our arms: 1 layer in BiSeNet-R18 (SpatialPath.conv_7x7), 3 in the dilated ResNet-50-v1c backbone (`--model
+r50` is that backbone here, as under --dilbn).  The off arm is the code path without the switch.
+
+    python tools/bench_infer.py --model r50 --stembn [--quick] [--reps 3]
+
+--stemlayers: per-layer figures, CACHE-WARM MICRO-BENCHMARKS as under --layers, for the 384 x 768 and 512 x 1024 maps
+(images of 768 x 1536 and 1024 x 2048).  The two image layers: (a) the vendor library's convolution + tsg_bn_apply_fwd
+(3x3 only: the 7x7 never runs there), (b) tsg_stem3_conv_fwd / tsg_stem_conv_fwd + tsg_bn_apply_fwd, (c) the fused call.
+The two inner deep-stem layers (64 -> 64, 64 -> 128): the vendor library's convolution + tsg_bn_apply_fwd against
+tsg_conv3x3_bnact_fwd.
+
+    python tools/bench_infer.py --stemlayers [--reps 3]
 """
 import argparse
 import copy
@@ -138,6 +153,7 @@ def event_times(fn, iters, warmup):
 
 # table -> (builder, title, prepare_inference's switch, attribute with the installed count, that count, module of fused_calls,
 #           what every one of our arms is prepared with besides)
+EVERY_OTHER = {"fuse_convbn": True, "fuse_dilated": True, "fuse_strided": True, "fuse_pointwise": True}
 ARM_MODELS = {"x39": (x39, "BiSeNet-X39", "fuse_separable", "fused_separable", 51, "sepconv", {}),
               "r18": (r18, "BiSeNet-R18", "fuse_convbn", "fused_convbn", 20, "convbn", {}),
               "r18+pwbn": (r18, "BiSeNet-R18, fuse_convbn=True", "fuse_pointwise", "fused_pointwise", 8, "pwbn",
@@ -149,7 +165,10 @@ ARM_MODELS = {"x39": (x39, "BiSeNet-X39", "fuse_separable", "fused_separable", 5
               "r18+s2bn": (r18, "BiSeNet-R18, fuse_convbn=True, fuse_pointwise=True", "fuse_strided", "fused_strided", 5,
                            "convbn:s2_fused_calls", {"fuse_convbn": True, "fuse_pointwise": True}),
               "r50+s2bn": (r50, "ResNet-50 backbone, fuse_convbn=True, fuse_pointwise=True", "fuse_strided", "fused_strided", 3,
-                           "convbn:s2_fused_calls", {"fuse_convbn": True, "fuse_pointwise": True})}
+                           "convbn:s2_fused_calls", {"fuse_convbn": True, "fuse_pointwise": True}),
+              "r18+stembn": (r18, "BiSeNet-R18, every other fusion on", "fuse_stem", "fused_stem", 1, "stembn", EVERY_OTHER),
+              "r50+stembn": (r50d, "dilated ResNet-50-v1c backbone, every other fusion on", "fuse_stem", "fused_stem", 3,
+                             "stembn", EVERY_OTHER)}
 
 
 def arm_times(arm, iters, warmup, model="x39"):
@@ -486,6 +505,91 @@ def s2_layers(reps):
     print(json.dumps({"device": torch.cuda.get_device_name(0), "layers": rows}))
 
 
+STEM_MAPS = ((768, 1536), (1024, 2048))              # the IMAGE; the stem's maps are 384 x 768 and 512 x 1024
+
+
+def stem_layers(reps):
+    """the image layers: (a) the vendor convolution + tsg_bn_apply_fwd (3x3 only), (b) tsg_stem*_conv_fwd + tsg_bn_apply_fwd,
+    (c) one launch; the two inner deep-stem layers: the vendor convolution + tsg_bn_apply_fwd against one launch"""
+    from torchseg_amd import _lib as L, kernels as K
+    kp = K.provider()
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(0)
+    CL = torch.channels_last
+    rows = []
+    cell = lambda t: "%.1f (%.1f-%.1f)" % (float(np.median(t)), min(t), max(t)) if t else "-"
+    print("CACHE-WARM MICRO-BENCHMARKS: one layer in a loop on the same tensors (%d calls per graph replay), us per call, median "
+          "of %d windows of >= 0.25 s (min-max), the variants alternated" % (GRAPH_CALLS, reps))
+    print("%-40s %-26s %-26s %-26s %-8s %-8s %s" % ("layer (image H x W or input map, Cin -> Cout)", "(a) conv2d + bn_apply",
+                                                     "(b) stem*_conv_fwd + bn_apply", "(c) fused", "c / a", "c / b",
+                                                     "model TB/s of (c)"))
+    for H, W in STEM_MAPS:
+        OH, OW = H // 2, W // 2
+        img = torch.randn(1, 3, H, W, generator=g).to(dev).bfloat16().contiguous()
+        y = torch.empty((1, 64, OH, OW), dtype=torch.bfloat16, device=dev, memory_format=CL)
+        fp = torch.stack([0.5 + torch.rand(64, generator=g), torch.randn(64, generator=g), torch.zeros(64)]).to(dev)
+        for k in (3, 7):
+            w = (torch.randn(64, 3, k, k, generator=g) * (2.0 / (3 * k * k)) ** 0.5).to(dev)
+            wb = w.bfloat16()
+            pack = kp.image_bnact_pack(w, fp)
+            unfused = kp.stem3_conv_fwd if k == 3 else kp.stem_conv_fwd
+
+            def vendor():
+                t = F.conv2d(img, wb, None, 2, k // 2).contiguous(memory_format=CL)
+                return kp.bn_apply_fwd(t, None, L.NHWC, 1, 64, OH * OW, fp, True, out=y)
+
+            def ours():
+                return kp.bn_apply_fwd(unfused(img, w), None, L.NHWC, 1, 64, OH * OW, fp, True, out=y)
+
+            def fused():
+                return kp.image_bnact_fwd(img, pack, k, True)
+
+            ref = fused().float()
+            db = (ours().float() - ref).abs().max().item()
+            da = (vendor().float() - ref).abs().max().item() if k == 3 else None
+            ga, gb, gc = graphed(vendor) if k == 3 else None, graphed(ours), graphed(fused)
+            ta, tb, tc = [], [], []
+            for _ in range(reps):
+                if k == 3:
+                    ta.append(1e3 * window_ms(ga) / GRAPH_CALLS)
+                tb.append(1e3 * window_ms(gb) / GRAPH_CALLS)
+                tc.append(1e3 * window_ms(gc) / GRAPH_CALLS)
+            mb, mc = float(np.median(tb)), float(np.median(tc))
+            nbytes = 2 * (3 * H * W + OH * OW * 64)            # the image once, y once
+            rows.append(dict(layer="image %dx%d" % (k, k), H=H, W=W, vendor_us=ta, unfused_us=tb, fused_us=tc,
+                             max_abs_diff_vendor=da, max_abs_diff_unfused=db, model_bytes=nbytes))
+            print("%-40s %-26s %-26s %-26s %-8s %-8.3f %.2f" % ("image %dx%d, 3 -> 64 %dx%d / 2" % (H, W, k, k), cell(ta), cell(tb),
+                                                                 cell(tc), "%.3f" % (mc / float(np.median(ta))) if ta else "-",
+                                                                 mc / mb, nbytes / mc / 1e6))
+        for Ci, Co in ((64, 64), (64, 128)):
+            x = torch.randn(1, Ci, OH, OW, generator=g).to(dev).bfloat16().contiguous(memory_format=CL)
+            w = (torch.randn(Co, Ci, 3, 3, generator=g) * (2.0 / (9 * Ci)) ** 0.5).to(dev).contiguous(memory_format=CL)
+            wb = w.bfloat16().contiguous(memory_format=CL)
+            fpi = torch.stack([0.5 + torch.rand(Co, generator=g), torch.randn(Co, generator=g), torch.zeros(Co)]).to(dev)
+            pack = kp.conv3x3_bnact_pack(w, None, fpi)
+            yi = torch.empty((1, Co, OH, OW), dtype=torch.bfloat16, device=dev, memory_format=CL)
+
+            def vendor():
+                return kp.bn_apply_fwd(F.conv2d(x, wb, None, 1, 1), None, L.NHWC, 1, Co, OH * OW, fpi, True, out=yi)
+
+            def fused():
+                return kp.conv3x3_bnact_fwd(x, pack, Co, None, True)
+
+            da = (vendor().float() - fused().float()).abs().max().item()
+            ga, gc = graphed(vendor), graphed(fused)
+            ta, tc = [], []
+            for _ in range(reps):
+                ta.append(1e3 * window_ms(ga) / GRAPH_CALLS)
+                tc.append(1e3 * window_ms(gc) / GRAPH_CALLS)
+            mc = float(np.median(tc))
+            nbytes = 2 * (OH * OW * (Ci + Co) + 9 * Ci * Co)
+            rows.append(dict(layer="inner 3x3", H=OH, W=OW, Cin=Ci, Cout=Co, vendor_us=ta, fused_us=tc, max_abs_diff_vendor=da,
+                             model_bytes=nbytes))
+            print("%-40s %-26s %-26s %-26s %-8.3f %-8s %.2f" % ("map %dx%d, %d -> %d 3x3 / 1" % (OH, OW, Ci, Co), cell(ta), "-",
+                                                                 cell(tc), mc / float(np.median(ta)), "-", nbytes / mc / 1e6))
+    print(json.dumps({"device": torch.cuda.get_device_name(0), "layers": rows}))
+
+
 def host_time(fn, iters, warmup):
     for _ in range(warmup):
         fn()
@@ -596,14 +700,24 @@ def main():
                          "BatchNorm layers off / on")
     ap.add_argument("--s2layers", action="store_true",
                     help="per-layer micro-benchmarks of the fused stride-2 3x3 conv + BatchNorm kernel")
+    ap.add_argument("--stembn", action="store_true",
+                    help="r18, r50 (here the dilated ResNet-50-v1c backbone): the arm table with every other fusion on and the "
+                         "fused image stems / deep stem off / on")
+    ap.add_argument("--stemlayers", action="store_true",
+                    help="per-layer micro-benchmarks of the fused image kernels and of the deep stem's inner layers")
     ap.add_argument("--iters", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=10)
     a = ap.parse_args()
     if a.dilbn and a.model != "r50":
         ap.error("--dilbn belongs to --model r50 (the dilated ResNet-50-v1c backbone)")
-    if sum((a.convbn, a.layers, a.pwbn, a.pwlayers, a.dilbn, a.dillayers, a.s2bn, a.s2layers)) > 1:
-        ap.error("--convbn, --layers, --pwbn, --pwlayers, --dilbn, --dillayers, --s2bn and --s2layers are separate "
-                 "measurements: one per call")
+    if sum((a.convbn, a.layers, a.pwbn, a.pwlayers, a.dilbn, a.dillayers, a.s2bn, a.s2layers, a.stembn, a.stemlayers)) > 1:
+        ap.error("--convbn, --layers, --pwbn, --pwlayers, --dilbn, --dillayers, --s2bn, --s2layers, --stembn and --stemlayers "
+                 "are separate measurements: one per call")
+    if a.stemlayers:
+        stem_layers(max(3, a.reps))
+        return
+    if a.stembn and a.model == "x39":
+        ap.error("--stembn belongs to --model r18 or --model r50")
     if a.dillayers:
         dil_layers(max(3, a.reps))
         return
@@ -618,8 +732,9 @@ def main():
         ap.error("--convbn and --layers are two measurements: one per call")
     if a.pwbn and a.model == "x39":
         ap.error("--pwbn belongs to --model r18 or --model r50")
-    if a.model == "r50" and not (a.pwbn or a.pwlayers or a.dilbn or a.s2bn):
-        ap.error("--model r50 has the --pwbn, --dilbn and --s2bn arm tables (and --pwlayers, --dillayers, --s2layers) only")
+    if a.model == "r50" and not (a.pwbn or a.pwlayers or a.dilbn or a.s2bn or a.stembn):
+        ap.error("--model r50 has the --pwbn, --dilbn, --s2bn and --stembn arm tables (and --pwlayers, --dillayers, --s2layers, "
+                 "--stemlayers) only")
     if sum((a.convbn, a.layers, a.pwbn, a.pwlayers)) > 1:
         ap.error("--convbn, --layers, --pwbn and --pwlayers are separate measurements: one per call")
     if a.pwlayers:
@@ -628,9 +743,9 @@ def main():
     if a.model == "r18" and a.layers:
         r18_layers(max(3, a.reps))
         return
-    if a.model == "x39" or a.convbn or a.pwbn or a.dilbn or a.s2bn or a.arm is not None:
+    if a.model == "x39" or a.convbn or a.pwbn or a.dilbn or a.s2bn or a.stembn or a.arm is not None:
         iters = a.iters or (10 if a.quick else 100)
-        table = a.model + ("+pwbn" if a.pwbn else "+dilbn" if a.dilbn else "+s2bn" if a.s2bn else "")
+        table = a.model + ("+pwbn" if a.pwbn else "+dilbn" if a.dilbn else "+s2bn" if a.s2bn else "+stembn" if a.stembn else "")
         if a.arm is not None:
             print(json.dumps(arm_times(a.arm, iters, a.warmup, table)))
         else:

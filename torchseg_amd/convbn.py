@@ -59,7 +59,8 @@ that hold a stride-2 layer (or a dilated one with `dilated=True`).  Without `str
 changes, and a stride-2 layer is never fused behind a module installed without it.  `s2_fused_calls` counts the launches
 of the stride-2 kernel.  seg_oprs.cbr_chain (our SpatialPath) runs its modules one after the other when gradients are
 disabled and a link is an eval-mode module with the strided behaviour on, so that the re-classed forward is what runs.
-The deep stem's 3x3 layers stay unfused, as does anything with C_in = 3.
+The deep stem's three 3x3 layers and the 7x7 image stem of a ConvBnRelu are not taken here: torchseg_amd/stembn.py
+(`install_fused_stem`, TSG_STEMBN_FUSED) fuses them, the two inner deep-stem layers on this file's kernel, gates and pack cache.
 
 TSG_CONVBN_FUSED=0|1 (default 0) is read by torchseg_amd.infer.prepare_inference(fuse_convbn=None), TSG_DILBN_FUSED=0|1
 (default 0) by prepare_inference(fuse_dilated=None), TSG_S2BN_FUSED=0|1 (default 0) by prepare_inference(fuse_strided=None);
@@ -171,8 +172,9 @@ class _FusedConvBn:
                                         # module re-classed earlier (by a plain install, behind pwbn's mixin or not) is upgraded
                                         # without a second re-classing; no parameter, buffer or state-dict key
 
-    def _cbn_pack(self, slot, conv, bn, x):
-        """the constants of layer `slot` for x's device and dtype, or None when they are stale and a capture is running"""
+    def _cbn_pack(self, slot, conv, bn, x, build=None):
+        """the constants of layer `slot` for x's device and dtype, or None when they are stale and a capture is running;
+        `build(kp, conv, fp)` makes a pack other than conv3x3_bnact_pack's (stembn.py: the image convolutions)"""
         srcs = (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)
         stamp = tuple((t._version, t.data_ptr()) if t is not None else None for t in srcs) + (bn.eps, conv.dilation[0], conv.stride[0])
         cache = self.__dict__.setdefault("_tsg_cbn_packs", {})
@@ -189,8 +191,11 @@ class _FusedConvBn:
             gamma = bn.weight.float() if bn.weight is not None else None
             beta = bn.bias.float() if bn.bias is not None else None
             fp = kp.bn_affine(mean, invstd, gamma, beta)
-            pack = _Pack(kp.conv3x3_bnact_pack(conv.weight, conv.bias, fp))    # the filter depends on neither
-            pack.dilation, pack.stride = conv.dilation[0], conv.stride[0]
+            if build is not None:
+                pack = build(kp, conv, fp)
+            else:
+                pack = _Pack(kp.conv3x3_bnact_pack(conv.weight, conv.bias, fp))    # the filter depends on neither
+                pack.dilation, pack.stride = conv.dilation[0], conv.stride[0]
         cache[key] = (stamp, pack)
         return pack
 

@@ -150,6 +150,88 @@ __global__ __launch_bounds__(256) void ds_fwd_k(const bf16_t* __restrict__ x, co
   }
 }
 
+// ---------------------------------------------------------------- forward + BatchNorm (+ ReLU), inference form
+// ds_fwd_k with the eval-mode BatchNorm of the layer behind it (ResNet._stem c[1], c[2]) applied to the fp32
+// accumulators: y = bf16(relu?(fma(a[oc], u, b[oc]))), one rounding, at the store into the LDS image.  ab = rows 0 and 1
+// of tsg_bn_affine's pack ([2][64] fp32, 16-byte aligned).  A lane's 32 channels are eight runs of four
+// (32 mt + 8 gq + 4 half ..): eight float4 loads per row, issued with the patch fetch, before the MFMAs.  The only
+// traffic ds_fwd_k does not have is those 512 bytes per block (cache hits); the separate BatchNorm pass over y is gone.
+// __launch_bounds__(256, 4): the 64 coefficient registers on top of ds_fwd_k's 72 gave 136 = three blocks per CU; bounded
+// the kernel takes 122, spill-free, four blocks per CU (a bound of 5 spills 24 registers).
+__global__ __launch_bounds__(256, 4) void ds_bnact_fwd_k(const bf16_t* __restrict__ x, const bf16_t* __restrict__ wp,
+                                                      const float* __restrict__ ab, bf16_t* __restrict__ y, DsGeom g,
+                                                      int relu) {
+  __shared__ __attribute__((aligned(16))) bf16_t patch[DS_NP + 2];              // 3568 B
+  __shared__ __attribute__((aligned(16))) bf16_t outs[DS_TH * DS_TW * DS_OS];    // 18432 B
+  const int tid = threadIdx.x, lane = tid & 63, wr = tid >> 6, half = lane >> 5, p = lane & 31;
+  const DsTile t = ds_tile(g, blockIdx.x);
+
+  bf16_t rp[DS_NPF];
+  ds_fetch_patch(x, g, t, tid, rp);
+  bf16x8 fw[2][2];                                     // [k-step][oc half]
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+      fw[ks][mt] = *reinterpret_cast<const bf16x8*>(wp + (mt * 32 + p) * DS_KP + ks * 16 + half * 8);
+  float4 ca[2][4], cb[2][4];                           // a, b of channels 32 mt + 8 gq + 4 half + 0..3
+#pragma unroll
+  for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+    for (int gq = 0; gq < 4; ++gq) {
+      ca[mt][gq] = *reinterpret_cast<const float4*>(ab + 32 * mt + 8 * gq + 4 * half);
+      cb[mt][gq] = *reinterpret_cast<const float4*>(ab + DS_OC + 32 * mt + 8 * gq + 4 * half);
+    }
+  ds_store_patch(patch, tid, rp);
+  __syncthreads();
+
+  f32x16 acc[2];
+#pragma unroll
+  for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[mt][r] = 0.f;
+  const bf16_t* base = patch + 2 * wr * DS_PC + 2 * p;
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks) {
+    int off[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) off[j] = ds_tap_off(ks * 16 + half * 8 + j);
+    const bf16x8 fb = ds_gather8(base, off, 0);
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[ks][mt], fb, acc[mt], 0, 0, 0);
+  }
+  // acc[mt][r]: oc = 32 mt + (r & 3) + 8 (r >> 2) + 4 half, pixel = (row wr, column p)
+#pragma unroll
+  for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+    for (int gq = 0; gq < 4; ++gq) {
+      float v[4];
+      v[0] = fmaf(ca[mt][gq].x, acc[mt][4 * gq + 0], cb[mt][gq].x);
+      v[1] = fmaf(ca[mt][gq].y, acc[mt][4 * gq + 1], cb[mt][gq].y);
+      v[2] = fmaf(ca[mt][gq].z, acc[mt][4 * gq + 2], cb[mt][gq].z);
+      v[3] = fmaf(ca[mt][gq].w, acc[mt][4 * gq + 3], cb[mt][gq].w);
+      if (relu) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
+      }
+      uint2 o;
+      o.x = pack2_bf16(v[0], v[1]);
+      o.y = pack2_bf16(v[2], v[3]);
+      *reinterpret_cast<uint2*>(outs + (wr * DS_TW + p) * DS_OS + 32 * mt + 8 * gq + 4 * half) = o;
+    }
+  __syncthreads();
+  // thread -> (pixel column spl, 16-B part spart) of each tile row: a wave stores 1 KB of consecutive NHWC bytes
+  const int spl = tid >> 3, spart = tid & 7;
+  if (t.ow0 + spl < g.OW) {
+    bf16_t* yt = y + (((int64_t)t.b * g.OH + t.oh0) * g.OW + t.ow0 + spl) * DS_OC + spart * 8;
+#pragma unroll
+    for (int qd = 0; qd < DS_TH; ++qd)
+      if (t.oh0 + qd < g.OH)
+        *reinterpret_cast<uint4*>(yt + (int64_t)qd * g.OW * DS_OC) =
+            *reinterpret_cast<const uint4*>(outs + (qd * DS_TW + spl) * DS_OS + spart * 8);
+  }
+}
+
 // ---------------------------------------------------------------- weight gradient
 // D[oc][k] = sum_pixel dy^T[oc][pixel] * im2col[pixel][k]: the GEMM K axis is the pixel axis.  dy is transposed
 // through LDS; wave wr sums the 32 pixels of tile row wr (two k-steps of 16) for both oc halves.  Persistent blocks
@@ -292,6 +374,33 @@ int tsg_stem3_conv_fwd(const void* x, const float* w, void* y, int64_t B, int64_
   hipLaunchKernelGGL(ds_pack_w, dim3((DS_OC * DS_KP + 255) / 256), dim3(256), 0, st, w, wp);
   TSG_CHECK_LAUNCH();
   hipLaunchKernelGGL(ds_fwd_k, dim3(g.ntiles), dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)wp, (bf16_t*)y, g);
+  TSG_CHECK_LAUNCH();
+  return 0;
+}
+
+int tsg_stem3_conv_bnact_supported(int dtype, int64_t B, int64_t H, int64_t W) {
+  DsGeom g;
+  return dtype == TSG_BF16 && ds_geom(B, H, W, &g);
+}
+
+size_t tsg_stem3_conv_bnact_filter_bytes(void) { return DS_WP_BYTES; }
+
+int tsg_stem3_conv_bnact_pack(const float* w, void* wp, void* stream) {
+  if (!w || !wp) return TSG_E_NULL;
+  if (!aligned16(wp) || (((uintptr_t)w) & 3u)) return TSG_E_ALIGN;
+  hipLaunchKernelGGL(ds_pack_w, dim3((DS_OC * DS_KP + 255) / 256), dim3(256), 0, (hipStream_t)stream, w, (bf16_t*)wp);
+  TSG_CHECK_LAUNCH();
+  return 0;
+}
+
+int tsg_stem3_conv_bnact_fwd(const void* x, const void* wp, const float* ab, void* y, int64_t B, int64_t H, int64_t W,
+                             int relu, void* stream) {
+  if (!x || !wp || !ab || !y) return TSG_E_NULL;
+  DsGeom g;
+  if (!ds_geom(B, H, W, &g)) return TSG_E_SHAPE;
+  if (!aligned16(y) || !aligned16(wp) || !aligned16(ab) || (((uintptr_t)x) & 1u)) return TSG_E_ALIGN;
+  hipLaunchKernelGGL(ds_bnact_fwd_k, dim3(g.ntiles), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
+                     (const bf16_t*)wp, ab, (bf16_t*)y, g, relu ? 1 : 0);
   TSG_CHECK_LAUNCH();
   return 0;
 }

@@ -216,8 +216,112 @@ __global__ __launch_bounds__(256) void stem_fwd_k(const bf16_t* __restrict__ x, 
   }
 }
 
+// ---------------------------------------------------------------- forward + BatchNorm (+ ReLU), inference form
+// stem_fwd_k<false> with the eval-mode BatchNorm of the ConvBnRelu around it (SpatialPath.conv_7x7) applied to the fp32
+// accumulators: y = bf16(relu?(fma(a[oc], u, b[oc]))), one rounding, at the store into the LDS image.  ab = rows 0 and 1
+// of tsg_bn_affine's pack ([2][64] fp32, 16-byte aligned).  A lane's 16 channels are four runs of four
+// (32 wm + 8 gq + 4 half ..): four float4 loads per row, once per block, kept in registers over the tile loop.  No
+// statistics.  The same tiles, grid and store as stem_fwd_k.
+// __launch_bounds__(256, 3): the grid is up to 768 = 3 x 256 persistent blocks that must all be resident, as stem_fwd_k's
+// are at 168 VGPRs.  Left to itself the compiler gave this kernel 200 (two blocks per CU: a third of the blocks would run
+// as a second round); bounded it takes 168, spill-free.
+__global__ __launch_bounds__(256, 3) void stem_bnact_fwd_k(const bf16_t* __restrict__ x, const bf16_t* __restrict__ wp,
+                                                        const float* __restrict__ ab, bf16_t* __restrict__ y, StemGeom g,
+                                                        int relu) {
+  __shared__ __attribute__((aligned(16))) uint32_t patch[SC_NPD];                 // 5616 B
+  __shared__ __attribute__((aligned(16))) bf16_t outs[SC_TH * SC_TW * 72];        // 18432 B: [pixel][64 oc + 8 pad]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, p = lane & 31;
+  const int wm = wave & 1, wr = wave >> 1;
+
+  bf16x8 fw[SC_KSTEPS];
+#pragma unroll
+  for (int t = 0; t < SC_KSTEPS; ++t)
+    fw[t] = *reinterpret_cast<const bf16x8*>(wp + (wm * 32 + p) * SC_KP + t * 16 + half * 8);
+  float4 ca[4], cb[4];                                 // a, b of channels 32 wm + 8 gq + 4 half + 0..3
+#pragma unroll
+  for (int gq = 0; gq < 4; ++gq) {
+    ca[gq] = *reinterpret_cast<const float4*>(ab + 32 * wm + 8 * gq + 4 * half);
+    cb[gq] = *reinterpret_cast<const float4*>(ab + SC_OC + 32 * wm + 8 * gq + 4 * half);
+  }
+
+  int rowoff[SC_KSTEPS];                               // patch row (in dwords) of this lane's K-fragment, tile row 0
+#pragma unroll
+  for (int t = 0; t < SC_KSTEPS; ++t) {
+    int r = 2 * t + half;
+    if (r >= 21) r = 0;                                // zero weights: any finite data will do
+    rowoff[t] = ((r / 7) * SC_PR + r % 7) * SC_PD + p;
+  }
+  const int spl = tid >> 3, spart = tid & 7;           // store: tile column spl, 16-B part spart
+
+  PatchLane pl;
+  patch_lane_init(g, tid, pl);
+  uint32_t rp[SC_NPF];
+  int tile = blockIdx.x;
+  TilePos tp = tile_pos(g, tile < g.ntiles ? tile : 0);
+  if (tile < g.ntiles) fetch_patch(x, g, tp, pl, rp);
+  for (; tile < g.ntiles; tile += gridDim.x) {
+    __syncthreads();                                   // the previous tile's reads of patch/outs are done
+#pragma unroll
+    for (int u = 0; u < SC_NPF; ++u)
+      if (tid + 256 * u < SC_NPD) patch[tid + 256 * u] = rp[u];
+    __syncthreads();
+    TilePos tn = tp;
+    if (tile + (int)gridDim.x < g.ntiles) {            // in flight during the MFMAs below
+      tn = tile_pos(g, tile + gridDim.x);
+      fetch_patch(x, g, tn, pl, rp);
+    }
+
+    f32x16 acc[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+#pragma unroll
+    for (int t = 0; t < SC_KSTEPS; ++t) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const uint32_t* q = patch + rowoff[t] + 2 * (2 * wr + i) * SC_PD;
+        union { uint32_t u[4]; bf16x8 v; } fb;
+        fb.u[0] = q[0]; fb.u[1] = q[1]; fb.u[2] = q[2]; fb.u[3] = q[3];
+        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[t], fb.v, acc[i], 0, 0, 0);
+      }
+    }
+
+    // acc[i][r]: oc = 32 wm + (r & 3) + 8 (r >> 2) + 4 half, pixel = (row 2 wr + i, column p).  Re-lay as [pixel][oc].
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int gq = 0; gq < 4; ++gq) {
+        const int oc0 = 32 * wm + 8 * gq + 4 * half;
+        float v[4];
+        v[0] = fmaf(ca[gq].x, acc[i][4 * gq + 0], cb[gq].x);
+        v[1] = fmaf(ca[gq].y, acc[i][4 * gq + 1], cb[gq].y);
+        v[2] = fmaf(ca[gq].z, acc[i][4 * gq + 2], cb[gq].z);
+        v[3] = fmaf(ca[gq].w, acc[i][4 * gq + 3], cb[gq].w);
+        if (relu) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
+        }
+        uint2 o;
+        o.x = pack2_bf16(v[0], v[1]);
+        o.y = pack2_bf16(v[2], v[3]);
+        *reinterpret_cast<uint2*>(outs + ((2 * wr + i) * SC_TW + p) * 72 + oc0) = o;
+      }
+    __syncthreads();
+    // thread -> (tile row qd, pixel spl, 16-B part spart): a wave stores 1 KB of consecutive NHWC bytes
+    bf16_t* yt = y + (((int64_t)tp.b * g.OH + tp.oh0) * g.OW + tp.ow0) * SC_OC;
+    const bool colok = tp.ow0 + spl < g.OW;
+#pragma unroll
+    for (int qd = 0; qd < SC_TH; ++qd)
+      if (tp.oh0 + qd < g.OH && colok)
+        *reinterpret_cast<uint4*>(yt + ((int64_t)qd * g.OW + spl) * SC_OC + spart * 8) =
+            *reinterpret_cast<const uint4*>(outs + (qd * SC_TW + spl) * 72 + spart * 8);
+    tp = tn;
+  }
+}
+
 // ---------------------------------------------------------------- weight gradient
-constexpr int SC_DS = 136;                 // dy^T row: 128 pixels + 8 pad (272 B, 16-B multiple)
+constexpr int SC_DS = 136;                // dy^T row: 128 pixels + 8 pad (272 B, 16-B multiple)
 constexpr int SC_RS = 24;                  // plane row stride in dwords (bank pattern: rows land 24 apart)
 constexpr int SC_RIC = 15;                 // plane rows per input channel (13 used); 15 = 7 mod 8 keeps r -> bank regular
 constexpr int SC_PLANE = 1088;             // dwords per plane copy (45 rows x 24 = 1080, rounded to 17 x 64)
@@ -974,6 +1078,34 @@ int tsg_stem_conv_fwd(const void* x, const float* w, void* y, int64_t B, int64_t
   const int grid = g.ntiles < 768 ? g.ntiles : 768;             // 3 resident blocks per CU (164 VGPRs)
   hipLaunchKernelGGL(stem_fwd_k<false>, dim3(grid), dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)wp, (bf16_t*)y, g,
                      (float*)nullptr);
+  TSG_CHECK_LAUNCH();
+  return 0;
+}
+
+int tsg_stem_conv_bnact_supported(int dtype, int64_t B, int64_t H, int64_t W) {
+  StemGeom g;
+  return dtype == TSG_BF16 && stem_geom(B, H, W, &g);
+}
+
+size_t tsg_stem_conv_bnact_filter_bytes(void) { return (size_t)SC_OC * SC_KP * sizeof(bf16_t); }
+
+int tsg_stem_conv_bnact_pack(const float* w, void* wp, void* stream) {
+  if (!w || !wp) return TSG_E_NULL;
+  if (!aligned16(wp) || (((uintptr_t)w) & 3u)) return TSG_E_ALIGN;
+  hipLaunchKernelGGL(stem_pack_w, dim3((SC_OC * SC_KP + 255) / 256), dim3(256), 0, (hipStream_t)stream, w, (bf16_t*)wp);
+  TSG_CHECK_LAUNCH();
+  return 0;
+}
+
+int tsg_stem_conv_bnact_fwd(const void* x, const void* wp, const float* ab, void* y, int64_t B, int64_t H, int64_t W,
+                            int relu, void* stream) {
+  if (!x || !wp || !ab || !y) return TSG_E_NULL;
+  StemGeom g;
+  if (!stem_geom(B, H, W, &g)) return TSG_E_SHAPE;
+  if (!aligned16(y) || !aligned16(wp) || !aligned16(ab) || (((uintptr_t)x) & 3u)) return TSG_E_ALIGN;
+  const int grid = g.ntiles < 768 ? g.ntiles : 768;             // stem_fwd_k's partition of the tiles
+  hipLaunchKernelGGL(stem_bnact_fwd_k, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
+                     (const bf16_t*)wp, ab, (bf16_t*)y, g, relu ? 1 : 0);
   TSG_CHECK_LAUNCH();
   return 0;
 }

@@ -99,9 +99,13 @@ upsample overrides.  Controlled by env so train.py needs no edit:
   TSG_S2BN_FUSED=0|1    (default 0; read by infer.prepare_inference only, never by this wrapper: with 1 the stride-2 3x3
                         convolutions -- BasicBlock.conv1 / Bottleneck.conv2 of the first block of layer2 / 3 / 4 and the detail
                         branch's two 3x3 layers; 5 in BiSeNet-R18, 3 in ResNet-50 -- run with their eval-mode BatchNorm and ReLU as
-                        one launch each at inference, one rounding instead of two; works with or without TSG_CONVBN_FUSED; the
-                        deep stem's 3x3 layers stay unfused, as does anything with C_in = 3.  Opt-in:
-                        profiles/s2bn_infer_bench.txt; convbn.py, csrc/s2bn.hip)
+                        one launch each at inference, one rounding instead of two; works with or without TSG_CONVBN_FUSED.
+                        Opt-in: profiles/s2bn_infer_bench.txt; convbn.py, csrc/s2bn.hip)
+  TSG_STEMBN_FUSED=0|1  (default 0; read by infer.prepare_inference only, never by this wrapper: with 1 the 7x7 image stem of
+                        SpatialPath and the three 3x3 layers of a v1c deep stem of width 64 run with their eval-mode BatchNorm
+                        and ReLU as one launch each at inference, one rounding instead of two, the image filters packed once
+                        instead of per call; 1 layer in BiSeNet-R18, 3 in PSPNet / PSANet / FCN.  Opt-in:
+                        profiles/stembn_infer_bench.txt; stembn.py, csrc/stemconv.hip, csrc/deepstem.hip)
   TSG_PWBN_FUSED=0|1    (default 0; read by infer.prepare_inference only, never by this wrapper: with 1 the 1x1 convolutions of the
                         Bottlenecks (conv1, conv3 with the block's shortcut and ReLU), the 1x1 stride-1 / stride-2 shortcuts and the
                         1x1 ConvBnRelu layers run with their eval-mode BatchNorm as one launch each at inference, one rounding

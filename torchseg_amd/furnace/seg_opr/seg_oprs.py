@@ -93,10 +93,12 @@ def cbr_chain(mods, x):
     # modules' own kernels anyway -- stem_bn_relu_conv returns None and bn_relu_conv runs `conv(norm_act(bn, relu, x))`
     # unless torch.is_grad_enabled() (torchseg_amd/convwrw.py: both conditions name it) -- so the module sequence is run
     # instead.  No call without such an install changes; with one, every link goes through its module, the last one (a 1x1
-    # that pwbn.install_fused_pointwise may have taken) included.
-    strided = (not torch.is_grad_enabled()
-               and any(getattr(m, "tsg_cbn_strided", False) and not m.training for m in mods))
-    if strided or not (x.is_cuda and all(isinstance(m, ConvBnRelu) and m.has_bn and m.has_relu for m in mods[:-1])):
+    # that pwbn.install_fused_pointwise may have taken) included.  The same holds for a link that
+    # torchseg_amd.stembn.install_fused_stem took (SpatialPath's 7x7 image stem, `tsg_stem_fused`).
+    own_forward = (not torch.is_grad_enabled()
+                   and any((getattr(m, "tsg_cbn_strided", False) or getattr(m, "tsg_stem_fused", False)) and not m.training
+                           for m in mods))
+    if own_forward or not (x.is_cuda and all(isinstance(m, ConvBnRelu) and m.has_bn and m.has_relu for m in mods[:-1])):
         for m in mods:
             x = m(x)
         return x

@@ -27,11 +27,18 @@
     before fuse_pointwise's: modules not yet re-classed that hold such a layer are re-classed, modules fuse_convbn
     re-classed are upgraded; csrc/s2bn.hip; `fused_strided` is the number of stride-2 LAYERS taken: 5 for BiSeNet-R18 with
     or without fuse_convbn, 3 for ResNet-50, 1 for PSPNet-R50).  With it our SpatialPath runs its ConvBnRelu modules one
-    after the other (seg_oprs.cbr_chain), so its conv_1x1 goes through its module and is fused by fuse_pointwise.  The
-    deep stem's 3x3 layers stay unfused, as does anything with C_in = 3.  Opt-in: profiles/s2bn_infer_bench.txt;
+    after the other (seg_oprs.cbr_chain), so its conv_1x1 goes through its module and is fused by fuse_pointwise.
+    Opt-in: profiles/s2bn_infer_bench.txt;
   - fuse_pointwise=True (default: TSG_PWBN_FUSED, 0): the 1x1 convolutions of the Bottlenecks, the 1x1 shortcuts and the 1x1
     ConvBnRelu layers run with their BatchNorm, shortcut and ReLU as one launch each
-    (torchseg_amd.pwbn.install_fused_pointwise, after convbn's install; csrc/pwbn.hip).  Opt-in.
+    (torchseg_amd.pwbn.install_fused_pointwise, after convbn's install; csrc/pwbn.hip).  Opt-in;
+  - fuse_stem=True (default: TSG_STEMBN_FUSED, 0): the 7x7 image stem of a ConvBnRelu (SpatialPath.conv_7x7) and the three
+    3x3 layers of a v1c deep stem of width 64 (ResNet._stem of FCN / PSPNet / PSANet / DFN / BiSeNet-R101) run with their
+    BatchNorm and ReLU as one launch each (torchseg_amd.stembn.install_fused_stem, after the four installs above;
+    stem_bnact_fwd_k in csrc/stemconv.hip, ds_bnact_fwd_k in csrc/deepstem.hip, and csrc/convbn.hip's kernel for the two
+    inner layers; `fused_stem` is the number of LAYERS taken: 1 for BiSeNet-R18, 3 for PSPNet / PSANet / FCN, 0 for a plain
+    ResNet-50).  The filters of the image layers are packed once, not per call.  With every switch on, a deep-stem
+    backbone runs no convolution outside our kernels.  Opt-in: profiles/stembn_infer_bench.txt.
 The `+=` / interpolate pre-sum and the ConvBnRelu chain fusions stay gated on autograd as in training (not enabled here).
 """
 import contextlib
@@ -50,7 +57,7 @@ def _compute_dtype(dtype):
 
 class InferenceModule(nn.Module):
     def __init__(self, network, dtype=None, channels_last=None, graph=False, fuse_separable=None, fuse_convbn=None,
-                 fuse_pointwise=None, fuse_dilated=None, fuse_strided=None):
+                 fuse_pointwise=None, fuse_dilated=None, fuse_strided=None, fuse_stem=None):
         super().__init__()
         from . import ddp
         from .syncbn import convert_syncbn_model
@@ -105,6 +112,12 @@ class InferenceModule(nn.Module):
         if fuse_pointwise:
             from .pwbn import install_fused_pointwise
             self.fused_pointwise = install_fused_pointwise(self.module)
+        if fuse_stem is None:
+            fuse_stem = ddp._env_flag("TSG_STEMBN_FUSED", False)
+        self.fused_stem = 0
+        if fuse_stem:                            # the image stems and the deep stem: modules none of the above re-classes
+            from .stembn import install_fused_stem
+            self.fused_stem = install_fused_stem(self.module)
         self.graph = bool(graph)
         self._graphs = {}
 
@@ -148,13 +161,13 @@ class InferenceModule(nn.Module):
 
 
 def prepare_inference(network, dtype=None, channels_last=None, graph=False, fuse_separable=None, fuse_convbn=None,
-                      fuse_pointwise=None, fuse_dilated=None, fuse_strided=None):
+                      fuse_pointwise=None, fuse_dilated=None, fuse_strided=None, fuse_stem=None):
     """See the module docstring.  `dtype`: torch.bfloat16 or torch.float32 (default: TSG_DTYPE, bf16)."""
     if isinstance(network, InferenceModule):
         return network
     return InferenceModule(network, dtype=dtype, channels_last=channels_last, graph=graph, fuse_separable=fuse_separable,
                            fuse_convbn=fuse_convbn, fuse_pointwise=fuse_pointwise, fuse_dilated=fuse_dilated,
-                           fuse_strided=fuse_strided)
+                           fuse_strided=fuse_strided, fuse_stem=fuse_stem)
 
 
 def pending_tail(out):

@@ -451,6 +451,53 @@ class HipKernels:
                L.stream_ptr(x))
         return dw
 
+    # ---- the image convolutions + BatchNorm (+ ReLU), inference form (stem_bnact_fwd_k / ds_bnact_fwd_k) ----
+    _IMAGE_BNACT = {7: "tsg_stem_conv_bnact", 3: "tsg_stem3_conv_bnact"}
+
+    def _image_bnact(self, ksize, what):
+        if ksize not in self._IMAGE_BNACT:
+            raise L.TsgError("image_bnact: a 7x7 or a 3x3 image convolution needed, not %r" % (ksize,))
+        return getattr(self.lib, self._IMAGE_BNACT[ksize] + "_" + what)
+
+    def image_bnact_supported(self, x, ksize):
+        """x [B,3,H,W] bf16 contiguous (NCHW); ksize 7 (3 -> 64, 7x7 / 2 / 3) or 3 (3 -> 64, 3x3 / 2 / 1)"""
+        if (ksize not in self._IMAGE_BNACT or x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.bfloat16
+                or not x.is_contiguous() or x.data_ptr() % (4 if ksize == 7 else 2)):
+            return False
+        return bool(self._image_bnact(ksize, "supported")(L.BF16, x.shape[0], x.shape[2], x.shape[3]))
+
+    def image_bnact_pack(self, weight, fp):
+        """weight fp32 [64,3,k,k] (k 7 or 3), fp = fwd_pack [>=2,64] fp32 of tsg_bn_affine -> (wp, ab): the bf16 filter in the
+        layout stem_pack_w / ds_pack_w build, packed once, and ab fp32 [2,64]"""
+        if (weight.dim() != 4 or tuple(weight.shape[:2]) != (64, 3) or weight.shape[2] != weight.shape[3]
+                or weight.shape[2] not in self._IMAGE_BNACT or weight.dtype != torch.float32
+                or fp.dtype != torch.float32 or fp.dim() != 2 or fp.shape[0] < 2 or fp.shape[1] != 64
+                or fp.device != weight.device):
+            raise L.TsgError("image_bnact_pack: a [64,3,7,7] or [64,3,3,3] fp32 weight and a fwd_pack [>=2,64] needed")
+        k = weight.shape[2]
+        w = weight.detach().contiguous()
+        wp = torch.empty(self._image_bnact(k, "filter_bytes")() // 2, dtype=torch.bfloat16, device=weight.device)
+        L.call(self._image_bnact(k, "pack"), w.data_ptr(), wp.data_ptr(), L.stream_ptr(w))
+        ab = torch.empty((2, 64), dtype=torch.float32, device=weight.device)
+        ab.copy_(fp[:2])
+        return wp, ab
+
+    def image_bnact_fwd(self, x, pack, ksize, relu):
+        """x [B,3,H,W] bf16 contiguous, pack = image_bnact_pack(...) of a k x k weight ->
+        y [B,64,(H-1)//2+1,(W-1)//2+1] bf16 channels_last, a new tensor"""
+        wp, ab = pack
+        fwd = self._image_bnact(ksize, "fwd")
+        if (wp.dtype != torch.bfloat16 or wp.numel() * 2 != self._image_bnact(ksize, "filter_bytes")()
+                or tuple(ab.shape) != (2, 64) or ab.dtype != torch.float32 or not ab.is_contiguous()):
+            raise L.TsgError("image_bnact_fwd: the pack does not belong to this convolution")
+        if x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.bfloat16 or not x.is_contiguous():
+            raise L.TsgError("image_bnact_fwd: a contiguous bf16 [B,3,H,W] image needed")
+        B, _, H, W = x.shape
+        y = torch.empty((B, 64, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=x.dtype, device=x.device,
+                        memory_format=torch.channels_last)
+        L.call(fwd, x.data_ptr(), wp.data_ptr(), ab.data_ptr(), y.data_ptr(), B, H, W, int(bool(relu)), L.stream_ptr(x))
+        return y
+
     def stem_conv_wrw_bn(self, x, da, xc, bp):
         """stem_conv_wrw of dy = BN+ReLU backward(da; xc, bp) without writing dy: x the image (as stem_conv_fwd), da / xc
         [B,64,OH,OW] bf16 channels_last (gradient w.r.t. relu(bn(xc)) / the stem output), bp fp32 [5,64] backward pack"""
