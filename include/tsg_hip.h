@@ -1048,6 +1048,46 @@ int tsg_conv3x3_s2_bnact_fwd(const void* x, const void* wf, const float* ab, con
                              int64_t H, int64_t W, int Cin, int Cout, int relu, void* stream);
 
 /* ------------------------------------------------------------------------
+ * PSPNet's pyramid pooling head without the concatenation, inference form (csrc/ppmbn.hip; the arithmetic and the plan:
+ * csrc/ppm_geom.h) — replaces, in eval mode, the chain n bilinear (align_corners) up-samplings -> torch.cat ->
+ * tsg_conv3x3_bnact_fwd over C + n Cb channels by three launches that never form the concatenated tensor:
+ *   T[b][cell][tap][oc] = sum_cb wb[s][tap][oc][cb] p_s[b][cell][cb]                          tsg_ppm_taps_fwd    (fp32)
+ *   E[b][oh][ow][oc]    = the interpolation of T summed over the taps whose pixel is inside    tsg_ppm_addend_fwd  (fp32 NHWC)
+ *   y                   = bf16( relu?( fma(ab[0], conv3x3(x, W[:, :C]) + E, ab[1]) ) )         tsg_conv3x3_bnact_add_fwd
+ * n <= 4 pooled maps p_s [B, sh[s], sw[s], Cb] bf16 channels_last, dense, 16-byte aligned (p_s for s >= n is ignored and may
+ * be NULL), sh[s] * sw[s] <= 64 cells each and sw[0] + ... + sw[n-1] <= 32 columns together; Cb % 16 == 0, Cout % 64 == 0.
+ * `cell` numbers the cells of all branches in order (branch, row, column), tap = 3 kh + kw.
+ * wb: the branch slices of the weight, bf16 [n][9][Cout][Cb] (the weight rounded to nearest even, as the convolution would
+ *   read it), 16-byte aligned, packed once per layer by the caller.
+ * T: fp32 [B][cells][9][Cout]; E: fp32 [B][H][W][Cout]; both 16-byte aligned, in a workspace of the caller's:
+ *   tsg_ppm_ws_bytes (0: a shape outside the set) holds T at offset 0 and E at tsg_ppm_plan's out6[4].
+ * tsg_ppm_plan: out6 = {cells, columns, grid of the tap launch (one wave per image, branch, tap and 32 output channels), grid
+ *   of the addend launch (one block per image, output row and 64 output channels), offset of E, workspace bytes}.
+ * The interpolation weights are those of tsg_upsample_bilinear_ac_fwd (csrc/tsg_resample.h), formed in fp32.  A tap outside
+ * the map contributes nothing (the concatenated tensor is zero-padded as a whole).
+ * tsg_conv3x3_bnact_add_fwd: x, wf, ab, y and the shape limits exactly as for tsg_conv3x3_bnact_fwd (wf: the pack of the
+ *   weight slice W[:, :C]); addend: fp32 [B,H,W,Cout], 16-byte aligned, added to the fp32 accumulator before the affine map;
+ *   ONE rounding, at the store.  tsg_conv3x3_bnact_add_plan: as tsg_conv3x3_bnact_plan (69,504 B of LDS).
+ * tsg_ppm_supported: the whole chain (TSG_BF16, the three stages' limits with C input channels of x).  Each X_supported is the
+ * single statement of what X_fwd takes.  Every fwd returns TSG_E_NULL, then TSG_E_SHAPE, then TSG_E_ALIGN, all before any
+ * launch.  No atomics, no sum split across blocks, no device query, no environment switch: bit-identical from launch to
+ * launch.  No host synchronisation and no allocation: capturable in a graph. */
+int    tsg_ppm_supported(int dtype, int64_t B, int64_t H, int64_t W, int n, const int* sh, const int* sw, int C, int Cb,
+                         int Cout);
+size_t tsg_ppm_ws_bytes(int64_t B, int64_t H, int64_t W, int n, const int* sh, const int* sw, int Cb, int Cout);
+int    tsg_ppm_plan(int64_t B, int64_t H, int64_t W, int n, const int* sh, const int* sw, int Cb, int Cout, int64_t* out6);
+int    tsg_ppm_taps_supported(int dtype, int64_t B, int n, const int* sh, const int* sw, int Cb, int Cout);
+int    tsg_ppm_taps_fwd(const void* p0, const void* p1, const void* p2, const void* p3, const void* wb, float* T, int64_t B,
+                        int n, const int* sh, const int* sw, int Cb, int Cout, void* stream);
+int    tsg_ppm_addend_supported(int64_t B, int64_t H, int64_t W, int n, const int* sh, const int* sw, int Cout);
+int    tsg_ppm_addend_fwd(const float* T, float* E, int64_t B, int64_t H, int64_t W, int n, const int* sh, const int* sw,
+                          int Cout, void* stream);
+int    tsg_conv3x3_bnact_add_supported(int dtype, int64_t B, int64_t H, int64_t W, int Cin, int Cout);
+int    tsg_conv3x3_bnact_add_plan(int64_t B, int64_t H, int64_t W, int Cin, int Cout, int* out5);
+int    tsg_conv3x3_bnact_add_fwd(const void* x, const void* wf, const float* ab, const float* addend, void* y, int64_t B,
+                                 int64_t H, int64_t W, int Cin, int Cout, int relu, void* stream);
+
+/* ------------------------------------------------------------------------
  * 1x1 convolution + BatchNorm (+ residual) (+ ReLU), inference form (csrc/pwbn.hip) — replaces, in eval mode, the chain
  * 1x1 convolution -> tsg_bn_apply_fwd of Bottleneck.conv1 / conv3 (furnace/base_model/resnet.py:80-101), of the 1x1
  * `downsample` shortcuts (:21-31) and of the 1x1 ConvBnRelu layers (seg_oprs.py:24-46) by one launch:

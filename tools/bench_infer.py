@@ -85,6 +85,21 @@ The two inner deep-stem layers (64 -> 64, 64 -> 128): the vendor library's convo
 tsg_conv3x3_bnact_fwd.
 
     python tools/bench_infer.py --stemlayers [--reps 3]
+
+--model psp --ppmbn: the arm table of the WHOLE PSPNet-R50 (workloads.pspnet.PSPNet, 19 classes, eval form: backbone,
+pyramid pooling head, classifier, the up-sampled log-probabilities materialised) with the concat-free pyramid pooling head
+(prepare_inference(fuse_pyramid=), csrc/ppmbn.hip) off and on, every other fusion (fuse_convbn, fuse_dilated, fuse_strided,
+fuse_pointwise, fuse_stem) on in every one of our arms.  The off arm is the code path without the switch.
+
+    python tools/bench_infer.py --model psp --ppmbn [--quick] [--reps 3]
+
+--ppmlayers: per-head figures, CACHE-WARM MICRO-BENCHMARKS as under --layers, at B = 1 on the 60 x 60, 96 x 192 and 128 x 256
+maps with C = 2048, from the four pooled maps on: (s) the stock head as a network runs it (four bilinear up-samplings +
+torch.cat + a 4096 -> 512 3x3 ConvBnRelu module behind prepare_inference(fuse_convbn=True), on whatever path its gate takes)
+and (a) the same chain with tsg_conv3x3_bnact_fwd called on the concatenated tensor made channels_last (that convolution alone
+beside it) against (b) tsg_ppm_taps_fwd + tsg_ppm_addend_fwd + tsg_conv3x3_bnact_add_fwd, and the three stages of (b) alone.
+
+    python tools/bench_infer.py --ppmlayers [--reps 3]
 """
 import argparse
 import copy
@@ -125,6 +140,13 @@ def r50d():
     net.layer3.apply(partial(_nostride_dilate, dilate=2))
     net.layer4.apply(partial(_nostride_dilate, dilate=4))
     return net.eval()
+
+
+def psp():
+    """the whole PSPNet-R50: dilated ResNet-50-v1c backbone, pyramid pooling head, classifier"""
+    from torchseg_amd.workloads.pspnet import PSPNet
+    torch.manual_seed(0)
+    return PSPNet(19, None, None, nn.BatchNorm2d, depth=50).eval()
 
 
 def x39():
@@ -168,7 +190,9 @@ ARM_MODELS = {"x39": (x39, "BiSeNet-X39", "fuse_separable", "fused_separable", 5
                            "convbn:s2_fused_calls", {"fuse_convbn": True, "fuse_pointwise": True}),
               "r18+stembn": (r18, "BiSeNet-R18, every other fusion on", "fuse_stem", "fused_stem", 1, "stembn", EVERY_OTHER),
               "r50+stembn": (r50d, "dilated ResNet-50-v1c backbone, every other fusion on", "fuse_stem", "fused_stem", 3,
-                             "stembn", EVERY_OTHER)}
+                             "stembn", EVERY_OTHER),
+              "psp+ppmbn": (psp, "PSPNet-R50 (the whole network), every other fusion on", "fuse_pyramid", "fused_pyramid", 1,
+                            "ppmbn:pyramid_fused_calls", dict(EVERY_OTHER, fuse_stem=True))}
 
 
 def arm_times(arm, iters, warmup, model="x39"):
@@ -590,6 +614,99 @@ def stem_layers(reps):
     print(json.dumps({"device": torch.cuda.get_device_name(0), "layers": rows}))
 
 
+PPM_HEADS = ((60, 60), (96, 192), (128, 256))              # the 1/8 map of ADE's 480 x 480 crop, of 768 x 1536, of 1024 x 2048
+PPM_SCALES = (1, 2, 3, 6)
+
+
+def ppm_layers(reps):
+    """PSPNet's head at B = 1, C = 2048, 4 x 512 pooled channels, 512 outputs, from the pooled maps on: (a) today's chain,
+    four bilinear up-samplings + torch.cat + tsg_conv3x3_bnact_fwd over 4096 channels, against (b) the three launches of
+    csrc/ppmbn.hip, and those three on their own; (s) is the stock head as a network runs it today: the same up-samplings and
+    torch.cat, then a 4096 -> 512 3x3 ConvBnRelu module behind prepare_inference(fuse_convbn=True), which takes whatever
+    path its gate gives it for the concatenated tensor (the row says how many of its calls were tsg_conv3x3_bnact_fwd)"""
+    from seg_opr.seg_oprs import ConvBnRelu
+    from torchseg_amd import convbn, kernels as K
+    from torchseg_amd.infer import prepare_inference
+    from torchseg_amd.upsample import install_aten_overrides
+    install_aten_overrides()
+    kp = K.provider()
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(0)
+    CL = torch.channels_last
+    C, Cb, Cout, n = 2048, 512, 512, len(PPM_SCALES)
+    maps = [(s, s) for s in PPM_SCALES]
+    rows = []
+    print("CACHE-WARM MICRO-BENCHMARKS: one head in a loop on the same tensors (%d calls per graph replay), us per call, median "
+          "of %d windows of >= 0.25 s (min-max), the variants alternated" % (GRAPH_CALLS, reps))
+    print("%-10s %-26s %-24s %-24s %-24s %-20s %-20s %-24s %-8s %-8s %s"
+          % ("map", "(s) 4 up + cat + ConvBnRelu", "(a) 4 up + cat + conv4096", "conv4096 of (a) alone", "(b) taps+addend+conv_add",
+             "ppm_taps_fwd", "ppm_addend_fwd", "conv3x3_bnact_add_fwd", "b / s", "b / a", "addend stages / conv_add"))
+    torch.manual_seed(0)
+    stock_head = prepare_inference(ConvBnRelu(C + n * Cb, Cout, 3, 1, 1, has_bias=False, norm_layer=nn.BatchNorm2d).to(dev),
+                                   dtype=torch.bfloat16, fuse_convbn=True)
+    for H, W in PPM_HEADS:
+        x = torch.randn(1, C, H, W, generator=g).to(dev).bfloat16().contiguous(memory_format=CL)
+        ps = [torch.randn(1, Cb, s, s, generator=g).to(dev).bfloat16().contiguous(memory_format=CL) for s in PPM_SCALES]
+        w = (torch.randn(Cout, C + n * Cb, 3, 3, generator=g) * (2.0 / (9 * (C + n * Cb))) ** 0.5).to(dev)
+        fp = torch.stack([0.5 + torch.rand(Cout, generator=g), torch.randn(Cout, generator=g), torch.zeros(Cout)]).to(dev)
+        pack_all = kp.conv3x3_bnact_pack(w, None, fp)
+        pack_x = kp.conv3x3_bnact_pack(w[:, :C], None, fp)
+        wb = kp.ppm_pack_branches(w, C, n)
+        T, E = kp.ppm_workspace(x, maps, Cb, Cout)
+        xcat = torch.cat([x] + [F.interpolate(p, size=(H, W), mode="bilinear", align_corners=True) for p in ps], 1)
+        xcat = xcat.contiguous(memory_format=CL)
+
+        def stock():
+            cat = torch.cat([x] + [F.interpolate(p, size=(H, W), mode="bilinear", align_corners=True) for p in ps], 1)
+            return stock_head(cat)
+
+        def today():
+            cat = torch.cat([x] + [F.interpolate(p, size=(H, W), mode="bilinear", align_corners=True) for p in ps], 1)
+            return kp.conv3x3_bnact_fwd(cat.contiguous(memory_format=CL), pack_all, Cout, None, True)
+
+        def conv_all():
+            return kp.conv3x3_bnact_fwd(xcat, pack_all, Cout, None, True)
+
+        def taps():
+            return kp.ppm_taps_fwd(ps, wb, T)
+
+        def addend():
+            return kp.ppm_addend_fwd(T, maps, E)
+
+        def conv_add():
+            return kp.conv3x3_bnact_add_fwd(x, pack_x, Cout, E, True)
+
+        def ours():
+            taps()
+            addend()
+            return conv_add()
+
+        d = (today().float() - ours().float()).abs().max().item()
+        cat = torch.cat([x] + [F.interpolate(p, size=(H, W), mode="bilinear", align_corners=True) for p in ps], 1)
+        before = convbn.fused_calls(stock_head.module)
+        stock()
+        stock_fused = convbn.fused_calls(stock_head.module) - before      # 1: the module's call was tsg_conv3x3_bnact_fwd
+        cat_is = dict(dtype=str(cat.dtype), channels_last=cat.is_contiguous(memory_format=CL), nchw=cat.is_contiguous(),
+                      aligned16=cat.data_ptr() % 16 == 0)
+        fns = (stock, today, conv_all, ours, taps, addend, conv_add)
+        graphs = [graphed(f) for f in fns]                             # GRAPH_CALLS launches (or chains) per replay
+        times = [[] for _ in fns]
+        for _ in range(reps):
+            for t, gr in zip(times, graphs):
+                t.append(1e3 * window_ms(gr) / GRAPH_CALLS)
+        med = [float(np.median(t)) for t in times]
+        rows.append(dict(H=H, W=W, C=C, Cb=Cb, Cout=Cout, stock_us=times[0], today_us=times[1], conv4096_us=times[2],
+                         ours_us=times[3], taps_us=times[4], addend_us=times[5], conv_add_us=times[6], max_abs_diff=d,
+                         stock_module_fused_launches=stock_fused, cat_result=cat_is,
+                         plan=kp.ppm_plan(1, H, W, maps, Cb, Cout), conv_plan=kp.conv3x3_bnact_add_plan(1, H, W, C, Cout)))
+        cell = lambda m, t: "%.1f (%.1f-%.1f)" % (m, min(t), max(t))
+        print("%-10s %-26s %-24s %-24s %-24s %-20s %-20s %-24s %-8.3f %-8.3f %.3f"
+              % (("%dx%d" % (H, W),) + tuple(cell(m, t) for m, t in zip(med, times))
+                 + (med[3] / med[0], med[3] / med[1], (med[4] + med[5]) / med[6])))
+        print("           (s): torch.cat gave %s; %d of the ConvBnRelu module's calls was tsg_conv3x3_bnact_fwd" % (cat_is, stock_fused))
+    print(json.dumps({"device": torch.cuda.get_device_name(0), "heads": rows}))
+
+
 def host_time(fn, iters, warmup):
     for _ in range(warmup):
         fn()
@@ -682,7 +799,7 @@ def sliding(iters):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
-    ap.add_argument("--model", choices=("r18", "x39", "r50"), default="r18")
+    ap.add_argument("--model", choices=("r18", "x39", "r50", "psp"), default="r18")
     ap.add_argument("--reps", type=int, default=3, help="arm tables and --layers: how often off / on alternate")
     ap.add_argument("--arm", choices=ARMS, default=None, help="arm tables: run this one arm here (what a child is started with)")
     ap.add_argument("--convbn", action="store_true", help="r18: the arm table with the fused conv + BatchNorm layers off / on")
@@ -705,9 +822,23 @@ def main():
                          "fused image stems / deep stem off / on")
     ap.add_argument("--stemlayers", action="store_true",
                     help="per-layer micro-benchmarks of the fused image kernels and of the deep stem's inner layers")
+    ap.add_argument("--ppmbn", action="store_true",
+                    help="psp: the arm table of the whole PSPNet-R50 with every other fusion on and the concat-free pyramid "
+                         "pooling head off / on")
+    ap.add_argument("--ppmlayers", action="store_true",
+                    help="per-head micro-benchmarks of the pyramid pooling head: today's chain against the three new launches")
     ap.add_argument("--iters", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=10)
     a = ap.parse_args()
+    if a.ppmlayers:
+        if sum((a.convbn, a.layers, a.pwbn, a.pwlayers, a.dilbn, a.dillayers, a.s2bn, a.s2layers, a.stembn, a.stemlayers, a.ppmbn)):
+            ap.error("--ppmlayers is a measurement of its own: one per call")
+        ppm_layers(max(3, a.reps))
+        return
+    if a.ppmbn != (a.model == "psp"):
+        ap.error("--ppmbn belongs to --model psp, and --model psp has the --ppmbn arm table only")
+    if a.ppmbn and sum((a.convbn, a.layers, a.pwbn, a.pwlayers, a.dilbn, a.dillayers, a.s2bn, a.s2layers, a.stembn, a.stemlayers)):
+        ap.error("--ppmbn is a measurement of its own: one per call")
     if a.dilbn and a.model != "r50":
         ap.error("--dilbn belongs to --model r50 (the dilated ResNet-50-v1c backbone)")
     if sum((a.convbn, a.layers, a.pwbn, a.pwlayers, a.dilbn, a.dillayers, a.s2bn, a.s2layers, a.stembn, a.stemlayers)) > 1:
@@ -743,9 +874,9 @@ def main():
     if a.model == "r18" and a.layers:
         r18_layers(max(3, a.reps))
         return
-    if a.model == "x39" or a.convbn or a.pwbn or a.dilbn or a.s2bn or a.stembn or a.arm is not None:
+    if a.model == "x39" or a.convbn or a.pwbn or a.dilbn or a.s2bn or a.stembn or a.ppmbn or a.arm is not None:
         iters = a.iters or (10 if a.quick else 100)
-        table = a.model + ("+pwbn" if a.pwbn else "+dilbn" if a.dilbn else "+s2bn" if a.s2bn else "+stembn" if a.stembn else "")
+        table = a.model + ("+pwbn" if a.pwbn else "+dilbn" if a.dilbn else "+s2bn" if a.s2bn else "+stembn" if a.stembn else "+ppmbn" if a.ppmbn else "")
         if a.arm is not None:
             print(json.dumps(arm_times(a.arm, iters, a.warmup, table)))
         else:

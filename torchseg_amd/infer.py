@@ -38,7 +38,13 @@
     stem_bnact_fwd_k in csrc/stemconv.hip, ds_bnact_fwd_k in csrc/deepstem.hip, and csrc/convbn.hip's kernel for the two
     inner layers; `fused_stem` is the number of LAYERS taken: 1 for BiSeNet-R18, 3 for PSPNet / PSANet / FCN, 0 for a plain
     ResNet-50).  The filters of the image layers are packed once, not per call.  With every switch on, a deep-stem
-    backbone runs no convolution outside our kernels.  Opt-in: profiles/stembn_infer_bench.txt.
+    backbone runs no convolution outside our kernels.  Opt-in: profiles/stembn_infer_bench.txt;
+  - fuse_pyramid=True (default: TSG_PPMBN_FUSED, 0): PSPNet's pyramid pooling head runs without its four up-samplings and
+    its concatenation (torchseg_amd.ppmbn.install_fused_pyramid, after the five installs above; csrc/ppmbn.hip): the pooled
+    channels' share of `conv6[0]` is contracted on the pooled maps (tsg_ppm_taps_fwd, tsg_ppm_addend_fwd) and the full-map
+    3x3 convolution reads x alone, with that share added in its epilogue (tsg_conv3x3_bnact_add_fwd).  `fused_pyramid` is
+    the number of HEADS taken: 1 for PSPNet, 0 for BiSeNet, PSANet and FCN.  The pools, the branch convolutions and the
+    classifier run as before.  Opt-in: profiles/ppmbn_infer_bench.txt.
 The `+=` / interpolate pre-sum and the ConvBnRelu chain fusions stay gated on autograd as in training (not enabled here).
 """
 import contextlib
@@ -57,7 +63,7 @@ def _compute_dtype(dtype):
 
 class InferenceModule(nn.Module):
     def __init__(self, network, dtype=None, channels_last=None, graph=False, fuse_separable=None, fuse_convbn=None,
-                 fuse_pointwise=None, fuse_dilated=None, fuse_strided=None, fuse_stem=None):
+                 fuse_pointwise=None, fuse_dilated=None, fuse_strided=None, fuse_stem=None, fuse_pyramid=None):
         super().__init__()
         from . import ddp
         from .syncbn import convert_syncbn_model
@@ -118,6 +124,12 @@ class InferenceModule(nn.Module):
         if fuse_stem:                            # the image stems and the deep stem: modules none of the above re-classes
             from .stembn import install_fused_stem
             self.fused_stem = install_fused_stem(self.module)
+        if fuse_pyramid is None:
+            fuse_pyramid = ddp._env_flag("TSG_PPMBN_FUSED", False)
+        self.fused_pyramid = 0
+        if fuse_pyramid:                         # the pyramid pooling head: a module none of the above re-classes
+            from .ppmbn import install_fused_pyramid
+            self.fused_pyramid = install_fused_pyramid(self.module)
         self.graph = bool(graph)
         self._graphs = {}
 
@@ -161,13 +173,13 @@ class InferenceModule(nn.Module):
 
 
 def prepare_inference(network, dtype=None, channels_last=None, graph=False, fuse_separable=None, fuse_convbn=None,
-                      fuse_pointwise=None, fuse_dilated=None, fuse_strided=None, fuse_stem=None):
+                      fuse_pointwise=None, fuse_dilated=None, fuse_strided=None, fuse_stem=None, fuse_pyramid=None):
     """See the module docstring.  `dtype`: torch.bfloat16 or torch.float32 (default: TSG_DTYPE, bf16)."""
     if isinstance(network, InferenceModule):
         return network
     return InferenceModule(network, dtype=dtype, channels_last=channels_last, graph=graph, fuse_separable=fuse_separable,
                            fuse_convbn=fuse_convbn, fuse_pointwise=fuse_pointwise, fuse_dilated=fuse_dilated,
-                           fuse_strided=fuse_strided, fuse_stem=fuse_stem)
+                           fuse_strided=fuse_strided, fuse_stem=fuse_stem, fuse_pyramid=fuse_pyramid)
 
 
 def pending_tail(out):

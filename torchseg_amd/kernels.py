@@ -1138,6 +1138,109 @@ class HipKernels:
                B, H, W, Cin, Cout, int(bool(relu)), L.stream_ptr(x))
         return y
 
+    # ---- pyramid pooling head without the concatenation, inference form (csrc/ppmbn.hip) ----
+    @staticmethod
+    def _ppm_maps(maps):
+        """[(sh, sw), ...] -> (n, sh, sw) as the C entry points take them"""
+        maps = [tuple(int(v) for v in m) for m in maps]
+        return len(maps), (C.c_int * max(len(maps), 1))(*[m[0] for m in maps]), (C.c_int * max(len(maps), 1))(*[m[1] for m in maps])
+
+    def ppm_supported(self, x, maps, Cb, Cout):
+        """x [B,C,H,W] channels_last bf16, 16-byte aligned; maps = [(sh, sw), ...] of the pooled branches of Cb channels each;
+        Cout output channels: the whole chain of csrc/ppmbn.hip takes the head"""
+        if (x.dim() != 4 or x.dtype != torch.bfloat16 or x.data_ptr() % 16
+                or not x.is_contiguous(memory_format=torch.channels_last)):
+            return False
+        B, Cin, H, W = x.shape
+        n, sh, sw = self._ppm_maps(maps)
+        return bool(self.lib.tsg_ppm_supported(L.BF16, B, H, W, n, sh, sw, Cin, int(Cb), int(Cout)))
+
+    def ppm_plan(self, B, H, W, maps, Cb, Cout):
+        """(cells, columns, grid of the tap launch, grid of the addend launch, offset of E, workspace bytes)"""
+        n, sh, sw = self._ppm_maps(maps)
+        out = (C.c_int64 * 6)()
+        L.call(self.lib.tsg_ppm_plan, B, H, W, n, sh, sw, int(Cb), int(Cout), out)
+        return tuple(out)
+
+    def ppm_ws_bytes(self, B, H, W, maps, Cb, Cout):
+        """bytes of the workspace (T, then E) of one head call; 0: a shape outside the set"""
+        n, sh, sw = self._ppm_maps(maps)
+        return int(self.lib.tsg_ppm_ws_bytes(B, H, W, n, sh, sw, int(Cb), int(Cout)))
+
+    def ppm_workspace(self, x, maps, Cb, Cout):
+        """(T fp32 [B, cells, 9, Cout], E fp32 [B, H, W, Cout]): views of one new allocation of tsg_ppm_ws_bytes on x's device"""
+        B, _, H, W = x.shape
+        cells, _, _, _, e_off, nbytes = self.ppm_plan(B, H, W, maps, Cb, Cout)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        T = ws[:B * cells * 9 * Cout * 4].view(torch.float32).view(B, cells, 9, Cout)
+        E = ws[e_off:e_off + B * H * W * Cout * 4].view(torch.float32).view(B, H, W, Cout)
+        return T, E
+
+    def ppm_pack_branches(self, weight, Cin, n):
+        """weight [Cout, Cin + n Cb, 3, 3] fp32 (or bf16) -> the branch slices bf16 [n, 9, Cout, Cb] as tsg_ppm_taps_fwd reads
+        them (rounded to nearest even, as the convolution would read them)"""
+        if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or n < 1 or (weight.shape[1] - Cin) % n or weight.shape[1] <= Cin:
+            raise L.TsgError("ppm_pack_branches: a [Cout, Cin + n Cb, 3, 3] weight needed")
+        Cout, Cb = weight.shape[0], (weight.shape[1] - Cin) // n
+        w = weight.detach()[:, Cin:].reshape(Cout, n, Cb, 9).permute(1, 3, 0, 2)
+        return w.to(torch.bfloat16).contiguous()
+
+    def ppm_taps_fwd(self, pooled, wb, T):
+        """pooled: the n branch outputs p_s [B,Cb,sh,sw] bf16 channels_last; wb = ppm_pack_branches(...); T of ppm_workspace,
+        written: T[b][cell][tap][oc] = sum_cb wb[s][tap][oc][cb] p_s[b][cell][cb]"""
+        n = len(pooled)
+        if not 1 <= n <= 4 or wb.dim() != 4 or wb.dtype != torch.bfloat16 or not wb.is_contiguous() or wb.shape[0] != n:
+            raise L.TsgError("ppm_taps_fwd: one to four pooled maps and their branch pack needed")
+        Cout, Cb = wb.shape[2], wb.shape[3]
+        B = pooled[0].shape[0]
+        for p in pooled:
+            if (p.dim() != 4 or p.dtype != torch.bfloat16 or p.shape[0] != B or p.shape[1] != Cb or p.device != wb.device
+                    or not p.permute(0, 2, 3, 1).is_contiguous()):
+                raise L.TsgError("ppm_taps_fwd: the pooled maps must be dense bf16 channels_last [B,Cb,sh,sw]")
+        maps = [tuple(p.shape[2:]) for p in pooled]
+        cells = sum(h * w for h, w in maps)
+        if T.dtype != torch.float32 or tuple(T.shape) != (B, cells, 9, Cout) or not T.is_contiguous():
+            raise L.TsgError("ppm_taps_fwd: T must be fp32 [B, cells, 9, Cout]")
+        _, sh, sw = self._ppm_maps(maps)
+        ptrs = [p.data_ptr() for p in pooled] + [None] * (4 - n)
+        L.call(self.lib.tsg_ppm_taps_fwd, *ptrs, wb.data_ptr(), T.data_ptr(), B, n, sh, sw, Cb, Cout, L.stream_ptr(wb))
+        return T
+
+    def ppm_addend_fwd(self, T, maps, E):
+        """T fp32 [B, cells, 9, Cout] of ppm_taps_fwd -> E fp32 [B, H, W, Cout] (written): the pooled channels' share of the
+        3x3 convolution of the concatenated, zero-padded tensor"""
+        n, sh, sw = self._ppm_maps(maps)
+        cells = sum(int(h) * int(w) for h, w in maps)
+        if (T.dtype != torch.float32 or E.dtype != torch.float32 or T.dim() != 4 or E.dim() != 4 or not T.is_contiguous()
+                or not E.is_contiguous() or T.shape[0] != E.shape[0] or T.shape[1] != cells or T.shape[2] != 9
+                or T.shape[3] != E.shape[3]):
+            raise L.TsgError("ppm_addend_fwd: T fp32 [B, cells, 9, Cout] and E fp32 [B, H, W, Cout] needed")
+        B, H, W, Cout = E.shape
+        L.call(self.lib.tsg_ppm_addend_fwd, T.data_ptr(), E.data_ptr(), B, H, W, n, sh, sw, Cout, L.stream_ptr(T))
+        return E
+
+    def conv3x3_bnact_add_plan(self, B, H, W, Cin, Cout):
+        """as conv3x3_bnact_plan, of tsg_conv3x3_bnact_add_fwd"""
+        out = (C.c_int * 5)()
+        L.call(self.lib.tsg_conv3x3_bnact_add_plan, B, H, W, Cin, Cout, out)
+        return tuple(out)
+
+    def conv3x3_bnact_add_fwd(self, x, pack, Cout, addend, relu):
+        """x [B,Cin,H,W] bf16 channels_last, pack = conv3x3_bnact_pack(...), addend fp32 [B,H,W,Cout] ->
+        y = bf16(relu?(fma(a, conv3x3(x) + addend, b))) [B,Cout,H,W] bf16 channels_last, a new tensor"""
+        wf, ab = pack
+        B, Cin, H, W = x.shape
+        if (wf.numel() != 9 * Cin * Cout or wf.dtype != torch.bfloat16 or tuple(ab.shape) != (2, Cout)
+                or ab.dtype != torch.float32 or not ab.is_contiguous()):
+            raise L.TsgError("conv3x3_bnact_add_fwd: the pack does not belong to this convolution")
+        if (addend.dtype != torch.float32 or tuple(addend.shape) != (B, H, W, Cout) or not addend.is_contiguous()
+                or addend.device != x.device):
+            raise L.TsgError("conv3x3_bnact_add_fwd: the addend must be fp32 [B,H,W,Cout], dense, on x's device")
+        y = torch.empty((B, Cout, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+        L.call(self.lib.tsg_conv3x3_bnact_add_fwd, x.data_ptr(), wf.data_ptr(), ab.data_ptr(), addend.data_ptr(), y.data_ptr(),
+               B, H, W, Cin, Cout, int(bool(relu)), L.stream_ptr(x))
+        return y
+
     # ---- 1x1 convolution + BatchNorm (+ residual) (+ ReLU), inference form (csrc/pwbn.hip) ----
     def conv1x1_bnact_supported(self, x, Cout, stride=1):
         """x [B,Cin,H,W] channels_last bf16, 16-byte aligned; Cout output channels of a 1x1 / stride 1 or 2 convolution"""
